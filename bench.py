@@ -173,6 +173,29 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20        # --dump-outputs: at most 64 MiB of arrays in all
+DUMP_SEED = 0
+
+
+def dump_sample(n, k):
+    """Fixed, seeded choice of k of the n items of an output (sorted indices): the same items in every run with the same arguments."""
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(k, n), replace=False))
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: every array as DIR/<name>.npy (float32 / float64 only, DUMP_LIMIT_BYTES in all), so that the outputs of two
+    builds can be compared array for array."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"bench.py --dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"bench.py --dump-outputs: {name} is {a.dtype}, not float32 / float64")
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    log(f"bench.py: dumped {', '.join(f'{n}{list(a.shape)}' for n, a in arrays.items())} ({total / 2**20:.1f} MiB) to {out_dir}")
+
+
 def _make_tile(seed):
     from micro_sam_amd.synthetic import synthetic_tile
     return synthetic_tile(seed)
@@ -466,6 +489,14 @@ def bench_config3(args, rank, world, dev):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # the uint32 label volume of the last timed step (this rank's slices): 3 seeded slices in full, per-slice summaries of all
+        pick = dump_sample(Z, 3)
+        dump_outputs(args.dump_outputs, {
+            "labels": seg[pick].astype(np.float32),
+            "slice_seeds": (3000 + rank * Z + pick).astype(np.float64),
+            "max_label_per_slice": seg.reshape(Z, -1).max(axis=1).astype(np.float64),
+            "foreground_pixels_per_slice": (seg.reshape(Z, -1) > 0).sum(axis=1).astype(np.float64)})
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -550,7 +581,12 @@ def main():
     ap.add_argument("--fp8-side", action="store_true", help="also run the fp8-encoder configuration (BASELINE configs[4]) as a side run")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous check only: gloo, no GPU work, prints the JSON line with n_gpus = world size")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MiB: the label images and embeddings of a fixed seeded sample of its tiles, per-tile summaries of all of them)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args)
@@ -690,10 +726,11 @@ def main():
             if int(word.item()) != 0:
                 raise RuntimeError("connected-component labelling did not converge in 2 passes")
 
-    def step(timed: bool, index: int, uploads=None, serial: bool = False, wait_gather: bool = False, defer_flags: bool = False):
+    def step(timed: bool, index: int, uploads=None, serial: bool = False, wait_gather: bool = False, defer_flags: bool = False, keep=None):
         """timed=True: instrumented pass with a device sync after every stage (stage breakdown only);
         timed=False: the production path, no extra synchronisation.  uploads: host tiles to convert + upload inside the step
-        (the PCIe-inclusive pass), else the resident uint8 tiles of step `index` are used."""
+        (the PCIe-inclusive pass), else the resident uint8 tiles of step `index` are used.  keep: a dict that receives the step's
+        label tiles and embeddings (--dump-outputs)."""
         labels = torch.empty((n_tiles, 1024, 1024), dtype=torch.int32, device=dev)
         flags = []
         t0 = time.perf_counter()
@@ -778,6 +815,8 @@ def main():
         check_flags(keep=1 if defer_flags else 0)
         if timed:
             n_instances.extend(int(v) for v in labels.flatten(1).max(dim=1).values.tolist())
+        if keep is not None:
+            keep.update(labels=full, features=feats, first_tile=(index * n_tiles) % n_distinct)
         return host_labels if uploads is not None else full
 
     for k in range(args.warmup):
@@ -793,8 +832,9 @@ def main():
     lib.msam_profile_enable(1 if profile_in_timed_region else 0)
     stage["host_enqueue"] = 0.0
     t_start = time.perf_counter()
+    last = {}
     for k in range(args.steps):
-        step(False, args.warmup + k, defer_flags=not profile_in_timed_region)
+        step(False, args.warmup + k, defer_flags=not profile_in_timed_region, keep=last if k == args.steps - 1 else None)
         if profile_in_timed_region:
             collect()        # synchronises the step's kernel events (end of step: nothing left in flight anyway)
     check_flags()
@@ -803,6 +843,18 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t_start
     lib.msam_profile_enable(0)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the label tiles ([N * tiles, 1024, 1024], all ranks' when N > 1) and this rank's
+        # embeddings; 6 seeded tiles of rank 0 in full (4 MiB of labels + 4 MiB of embedding each), per-tile summaries of every label tile
+        pick = dump_sample(n_tiles, 6)
+        lab = last["labels"]
+        dump_outputs(args.dump_outputs, {
+            "labels": lab[torch.as_tensor(pick, device=dev)].float().cpu().numpy(),
+            "embeddings": last["features"][torch.as_tensor(pick, device=dev), 0].float().cpu().numpy(),
+            "tile_seeds": (1000 + rank * n_distinct + last["first_tile"] + pick).astype(np.float64),
+            "max_label_per_tile": lab.flatten(1).amax(dim=1).double().cpu().numpy(),
+            "foreground_pixels_per_tile": (lab.flatten(1) > 0).sum(dim=1).double().cpu().numpy()})
+    del last
     prof_steps = args.steps
     if not profile_in_timed_region:
         prof_steps = max(1, min(args.steps, 5))

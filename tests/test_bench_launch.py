@@ -129,3 +129,30 @@ def test_emit_prints_the_full_tree_before_the_final_line(tmp_path, monkeypatch, 
     full = json.load(open(tmp_path / "gpurun_out" / "bench_extras.json"))
     assert "other_kernels" in full["roofline"] and "worst" in full["mask_iou_vs_ref"]
     assert json.loads(lines[1])["extras"] == os.path.join("gpurun_out", "bench_extras.json")
+
+
+def test_steps_below_one_is_refused():
+    r = _run(["--steps", "0", "--dry-run"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_dump_outputs_writes_seeded_float_arrays_under_the_limit(tmp_path):
+    """bench.py --dump-outputs DIR: the same seeded sample of an output in every run, float32 / float64 .npy files, 64 MiB in all at most."""
+    import numpy as np
+    import pytest
+
+    import bench
+    pick = bench.dump_sample(64, 8)
+    assert len(pick) == 8 and list(pick) == sorted(set(pick.tolist())) and pick.max() < 64
+    assert np.array_equal(pick, bench.dump_sample(64, 8)) and len(bench.dump_sample(3, 8)) == 3
+    arrays = {"labels": np.arange(12, dtype=np.float32).reshape(3, 4), "tile_seeds": np.arange(3, dtype=np.float64) + 1000}
+    bench.dump_outputs(str(tmp_path / "d"), arrays)
+    assert sorted(os.listdir(tmp_path / "d")) == ["labels.npy", "tile_seeds.npy"]
+    for name, a in arrays.items():
+        b = np.load(tmp_path / "d" / f"{name}.npy")
+        assert b.dtype == a.dtype and np.array_equal(a, b)
+    with pytest.raises(TypeError):
+        bench.dump_outputs(str(tmp_path / "e"), {"labels": np.zeros(4, np.int32)})
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "f"), {"labels": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32)})
+    assert not (tmp_path / "f").exists()
