@@ -1,6 +1,6 @@
 """Benchmark of the hot path: 1024^2 tiles/s, embed + AMG (vit_b, bf16 MFMA operands), BASELINE.json config 2.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 N > 1: one rank per GPU over RCCL.  When the script is NOT already running under a launcher (no WORLD_SIZE in the
 environment) it re-executes itself under ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
@@ -10,7 +10,9 @@ One step = TILES_PER_STEP synthetic tiles per rank through: batched image encode
 initialize (32x32 grid prompts, fused mask post-processing to bit masks on the device) -> generate (default thresholds,
 box NMS, merge to a uint32 label image); with N > 1 the label tiles of all ranks are all-gathered (RCCL) inside the timed
 region.  Inputs (uint8 RGB tiles, output of util._to_image; 256 distinct tiles per rank, visited in order) are resident
-in HBM before the timed region.  Prints ONE JSON line on rank 0 with, next to the contract fields:
+in HBM before the timed region.  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints ONE JSON line on
+rank 0: the contract fields, `config` (and `roofline` with --lanes 1, whose kernel brackets run inside the timed region).  With
+--full it also runs everything else, after the timed region, and the line carries next to the contract fields:
 
   roofline          dominant kernel family of the timed region against the MFMA roofline SURVEY.md 8(d) defines
                     (algorithmic FLOP of the reference's formulation per launch / live HIP-event duration / 2.5 PFLOP/s);
@@ -23,6 +25,8 @@ in HBM before the timed region.  Prints ONE JSON line on rank 0 with, next to th
   config3_side / fp8_side / train_side   (N = 1, default run) BASELINE configs[2], [4], [3] as short side runs of this script /
                     tools/train_bench.py in their own processes after the timed region: the driver's record carries every named
                     configuration; `--no-side` or `--no-config-sides` skips them
+  config            + pipelined_labels_equal_serial (the pipelined step re-run against a serial instrumented step, which also gives
+                    instances_per_tile and stage_seconds_per_tile_synced_pass)
 """
 import argparse
 import ctypes as C
@@ -37,6 +41,7 @@ import torch
 import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
+T_IMPORTED = time.perf_counter()       # (the imports above are done: set-up time in the log is counted from here)
 sys.path.insert(0, ROOT)
 
 TILES_PER_STEP = 64     # 4 encoder batches of 16; the decode lanes start on a batch's tiles while the encoder works on the next batch
@@ -431,10 +436,10 @@ def config_sides(timeout_s: float = 420.0, fp8: bool = False):
     sides = {}
     # the parity-meeting precision mode in the headline's own harness: tiles resident in HBM, 3 decode lanes, label tiles in HBM (mask_iou_vs_ref_split16
     # carries its parity; its tiles_per_s_segment_slices is the host-array-in / host-volume-out rate of the same mode)
-    sides["split16_side"] = run(["bench.py", "--precision", "split16", "--no-cpu-baseline", "--no-side", "--steps", "2", "--warmup", "1", "--tiles-per-step", "32",
+    sides["split16_side"] = run(["bench.py", "--precision", "split16", "--full", "--no-cpu-baseline", "--no-side", "--steps", "2", "--warmup", "1", "--tiles-per-step", "32",
                                  "--distinct-tiles", "64", "--enc-batch", "8"], ("metric", "value", "unit", "ms_per_step"))
     if fp8:         # configs[4]: a precision mode, not a performance mode (rounds 3-5: 175 vs 170-174 tiles/s; DESIGN "fp8") - on request only
-        sides["fp8_side"] = run(["bench.py", "--encoder-dtype", "fp8", "--no-cpu-baseline", "--no-side", "--steps", "3", "--warmup", "1"],
+        sides["fp8_side"] = run(["bench.py", "--encoder-dtype", "fp8", "--full", "--no-cpu-baseline", "--no-side", "--steps", "3", "--warmup", "1"],
                                 ("metric", "value", "unit", "ms_per_step", "dtype"))
     sides["config3_side"] = run(["bench.py", "--workload", "config3", "--steps", "3", "--warmup", "1", "--slices", "8"],
                                 ("metric", "value", "unit", "ms_per_step", "dtype", "config"))
@@ -546,7 +551,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU reference leg (cpu_baseline, mask_iou_vs_ref)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the roofline pass, the pipelined-vs-serial label check, the side measurements, the CPU "
+                         "reference and parity legs and the side runs of the other named configurations (a plain run times the steps only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU reference leg (cpu_baseline, mask_iou_vs_ref)")
     ap.add_argument("--cpu-tiles", type=int, default=3, help="full tiles the CPU reference runs (median reported)")
     ap.add_argument("--glds", type=int, default=0)
     ap.add_argument("--tiles-per-step", type=int, default=TILES_PER_STEP, help="tiles per rank and step")
@@ -570,15 +578,15 @@ def main():
                     help="config2 (default): the headline metric; config3: BASELINE configs[2] per-slice path (vit_l, tiled 2048^2 slices)")
     ap.add_argument("--slices", type=int, default=8, help="--workload config3: slices per GPU and step")
     ap.add_argument("--no-side", action="store_true",
-                    help="skip the side measurements (pcie_inclusive, api_inclusive, rle_side, interactive_side): profiling runs, so "
+                    help="--full: skip the side measurements (pcie_inclusive, api_inclusive, rle_side, interactive_side): profiling runs, so "
                          "that per-kernel averages hold the hot path's launches only")
     ap.add_argument("--api-tiles", type=int, default=TILES_PER_STEP, help="tiles of the api_inclusive side measurement (default: one step's worth)")
     ap.add_argument("--no-config-sides", action="store_true",
-                    help="skip config3_side / fp8_side / train_side (the other named configurations as short side runs, N = 1 only)")
+                    help="--full: skip config3_side / fp8_side / train_side (the other named configurations as short side runs, N = 1 only)")
     ap.add_argument("--precision", choices=("default", "split16", "strict"), default="default",
                     help="precision mode of the timed region (predictor.set_precision): default = the headline's 16-bit path; split16 / strict = the reference's "
                          "formulation on fp16 operand pairs / fp32 kernels (side measurements: `split16_side` of the default run is this script with --precision split16)")
-    ap.add_argument("--fp8-side", action="store_true", help="also run the fp8-encoder configuration (BASELINE configs[4]) as a side run")
+    ap.add_argument("--fp8-side", action="store_true", help="--full: also run the fp8-encoder configuration (BASELINE configs[4]) as a side run")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous check only: gloo, no GPU work, prints the JSON line with n_gpus = world size")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -587,6 +595,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:           # a plain run: the headline figure only
+        args.no_side = args.no_cpu_baseline = args.no_config_sides = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args)
@@ -819,11 +829,13 @@ def main():
             keep.update(labels=full, features=feats, first_tile=(index * n_tiles) % n_distinct)
         return host_labels if uploads is not None else full
 
+    t_warm = time.perf_counter()
     for k in range(args.warmup):
         step(False, k)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    log(f"rank {rank}: set-up {t_warm - T_IMPORTED:.1f} s, warm-up {time.perf_counter() - t_warm:.1f} s")
     # Per-kernel HIP-event brackets (msam_profile_*) measure a kernel's own duration only when nothing else shares the GPU with
     # it.  With one decode lane they run inside the timed region; with several lanes kernels of different tiles overlap (that
     # is the point of the lanes) and a bracket would also count the time a launch queues behind another lane's kernels, so the
@@ -856,7 +868,8 @@ def main():
             "foreground_pixels_per_tile": (lab.flatten(1) > 0).sum(dim=1).double().cpu().numpy()})
     del last
     prof_steps = args.steps
-    if not profile_in_timed_region:
+    roofline_measured = profile_in_timed_region or args.full
+    if not profile_in_timed_region and args.full:
         prof_steps = max(1, min(args.steps, 5))
         host_enqueue_timed = stage["host_enqueue"]
         torch.cuda.synchronize()
@@ -869,20 +882,22 @@ def main():
         serial_elapsed = time.perf_counter() - t_ser
         lib.msam_profile_enable(0)
         stage["host_enqueue"] = host_enqueue_timed
-    serial_labels = step(True, 0).clone()     # one extra instrumented pass (outside the timed region): stage breakdown, and
-    pipelined_labels = step(False, 0, wait_gather=True)   # the serial result that the pipelined (lanes / side stream) step must reproduce
-    torch.cuda.synchronize()
-    labels_equal = bool(torch.equal(serial_labels, pipelined_labels))
-    if not labels_equal:
-        raise RuntimeError("bench.py: the pipelined step (lanes / side-stream generate) does not reproduce the serial labels")
+    if args.full:
+        serial_labels = step(True, 0).clone()     # one extra instrumented pass (outside the timed region): stage breakdown, and
+        pipelined_labels = step(False, 0, wait_gather=True)   # the serial result that the pipelined (lanes / side stream) step must reproduce
+        torch.cuda.synchronize()
+        labels_equal = bool(torch.equal(serial_labels, pipelined_labels))
+        if not labels_equal:
+            raise RuntimeError("bench.py: the pipelined step (lanes / side-stream generate) does not reproduce the serial labels")
     # PCIe-inclusive pass (outside the timed region): util._to_image + H2D of the uint8 tiles + label D2H inside the clock
-    torch.cuda.synchronize()
-    t_p = time.perf_counter()
     n_pcie = 0 if args.no_side else min(3, max(1, n_distinct // n_tiles))
-    for k in range(n_pcie):
-        step(False, k, uploads=tiles_np[k * n_tiles:(k + 1) * n_tiles])
-    torch.cuda.synchronize()
-    pcie_elapsed = time.perf_counter() - t_p
+    if n_pcie:
+        torch.cuda.synchronize()
+        t_p = time.perf_counter()
+        for k in range(n_pcie):
+            step(False, k, uploads=tiles_np[k * n_tiles:(k + 1) * n_tiles])
+        torch.cuda.synchronize()
+        pcie_elapsed = time.perf_counter() - t_p
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -918,31 +933,34 @@ def main():
                     "hbm_frac": None if g is None else round(g / PEAK_HBM_GBS, 4),
                     "avg_launch_mbytes": round(d["bytes"] / launches / 1e6, 2)}
 
-        fams = [fam(f) for f in range(NF) if prof[f]["launches"] > 0]
-        fams.sort(key=lambda r: -r["seconds_per_tile"])
-        # roofline of the dominant kernel (largest GPU time in the timed region); the others are kept alongside.
-        # `traffic`: HBM bytes per launch from the PMC passes of profiles/ (FETCH_SIZE / WRITE_SIZE, separate runs), when a
-        # table for this kernel is committed
-        dom = dict(fams[0]) if fams else {"bound": "mfma", "achieved": 0.0, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": 0.0}
-        traffic, traffic_source = pmc_traffic(dom.get("kernel", ""))
-        whole = TILE_TFLOP_ALGORITHMIC * value / world
-        roof = {"bound": dom["bound"], "achieved": dom["achieved"], "peak": dom["peak"], "unit": dom["unit"], "frac": dom["frac"],
-                "traffic": traffic, "traffic_source": traffic_source, **{k: v for k, v in dom.items() if k not in ("bound", "achieved", "peak", "unit", "frac")},
-                "whole_path_tflops": round(whole, 2), "whole_path_frac": round(whole / PEAK_BF16_TFLOPS, 4),
-                "measured_in": ("the timed region (one decode lane: no two kernels of the hot path share the GPU)" if profile_in_timed_region
-                                else f"a serial one-lane pass of {prof_steps} steps right after the timed region "
-                                     f"({n_tiles * prof_steps / serial_elapsed:.1f} tiles/s): in the timed region {len(lanes)} lanes "
-                                     "overlap the kernels of different tiles, so a HIP-event bracket there also counts queueing; "
-                                     "profiles/ holds the rocprofv3 summary of the same one-lane command (--lanes 1)"),
-                "other_kernels": fams[1:],
-                # why frac stops where it does (measured: profiles/r06_mfma_valu_overlap.md - the matrix pipe and the vector ALU of a SIMD DO overlap,
-                # round 5's "additive" reading came from a probe whose vector stream was dependent v_pk_fma_f32)
-                "pipes": ("MI355X, measured (tools/mfma_valu_overlap_probe2.hip, inline-asm streams): an MFMA-only and a VALU-only wave of one SIMD take 1.09 - 1.12 x the longer "
-                          "of the two in both age orders; two waves per SIMD hide up to 5 plain vector instructions per 32-cycle MFMA at 91 - 94 % matrix-pipe "
-                          "occupancy, beyond that the SIMD's vector ISSUE (~one instruction per 5.5 cycles between two waves) is the limit.  The dominant kernel "
-                          "carries 372 vector : 57 (16-cycle) matrix instructions per tile and wave: it is vector-issue-bound (profiles/r05_pmc_sq_counters.md: "
-                          "2 x 35 % VALU-active, 31 % MFMA-busy); `frac` is what its vector stream leaves of the matrix pipe.  Clock under this load: ~2.0 GHz "
-                          "(GRBM_GUI_ACTIVE / duration), not the 2.4 GHz of the nominal peak")}
+        if roofline_measured:
+            fams = [fam(f) for f in range(NF) if prof[f]["launches"] > 0]
+            fams.sort(key=lambda r: -r["seconds_per_tile"])
+            # roofline of the dominant kernel (largest GPU time in the timed region); the others are kept alongside.
+            # `traffic`: HBM bytes per launch from the PMC passes of profiles/ (FETCH_SIZE / WRITE_SIZE, separate runs), when a
+            # table for this kernel is committed
+            dom = dict(fams[0]) if fams else {"bound": "mfma", "achieved": 0.0, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": 0.0}
+            traffic, traffic_source = pmc_traffic(dom.get("kernel", ""))
+            whole = TILE_TFLOP_ALGORITHMIC * value / world
+            roof = {"bound": dom["bound"], "achieved": dom["achieved"], "peak": dom["peak"], "unit": dom["unit"], "frac": dom["frac"],
+                    "traffic": traffic, "traffic_source": traffic_source, **{k: v for k, v in dom.items() if k not in ("bound", "achieved", "peak", "unit", "frac")},
+                    "whole_path_tflops": round(whole, 2), "whole_path_frac": round(whole / PEAK_BF16_TFLOPS, 4),
+                    "measured_in": ("the timed region (one decode lane: no two kernels of the hot path share the GPU)" if profile_in_timed_region
+                                    else f"a serial one-lane pass of {prof_steps} steps right after the timed region "
+                                         f"({n_tiles * prof_steps / serial_elapsed:.1f} tiles/s): in the timed region {len(lanes)} lanes "
+                                         "overlap the kernels of different tiles, so a HIP-event bracket there also counts queueing; "
+                                         "profiles/ holds the rocprofv3 summary of the same one-lane command (--lanes 1)"),
+                    "other_kernels": fams[1:],
+                    # why frac stops where it does (measured: profiles/r06_mfma_valu_overlap.md - the matrix pipe and the vector ALU of a SIMD DO overlap,
+                    # round 5's "additive" reading came from a probe whose vector stream was dependent v_pk_fma_f32)
+                    "pipes": ("MI355X, measured (tools/mfma_valu_overlap_probe2.hip, inline-asm streams): an MFMA-only and a VALU-only wave of one SIMD take 1.09 - 1.12 x the longer "
+                              "of the two in both age orders; two waves per SIMD hide up to 5 plain vector instructions per 32-cycle MFMA at 91 - 94 % matrix-pipe "
+                              "occupancy, beyond that the SIMD's vector ISSUE (~one instruction per 5.5 cycles between two waves) is the limit.  The dominant kernel "
+                              "carries 372 vector : 57 (16-cycle) matrix instructions per tile and wave: it is vector-issue-bound (profiles/r05_pmc_sq_counters.md: "
+                              "2 x 35 % VALU-active, 31 % MFMA-busy); `frac` is what its vector stream leaves of the matrix pipe.  Clock under this load: ~2.0 GHz "
+                              "(GRBM_GUI_ACTIVE / duration), not the 2.4 GHz of the nominal peak")}
+        else:
+            roof = None          # (several decode lanes: the kernel brackets run in the serial pass of --full only)
         out = {
             "metric": {"bf16": "1024^2 tiles/s embed+AMG (vit_b bf16)",
                        "fp16": "1024^2 tiles/s embed+AMG (vit_b, fp16 instead of bf16 operands in the image encoder: side measurement)",
@@ -967,16 +985,17 @@ def main():
                        "parallelism": f"dp{world} tiles, all_gather of uint32 label tiles (RCCL, on a communication stream under the next step)" +
                                       (" (MSAM_FORCE_DIST: world-size-1 nccl group, the gather runs through RCCL)" if force_dist else ""),
                        "timed_region": "uint8 RGB tiles resident in HBM -> label tiles in HBM (all-gathered when N > 1); "
-                                       "util._to_image, H2D and label D2H are in pcie_inclusive, lazy RLE encoding in rle_side",
-                       "decode_lanes": len(lanes), "pipelined_labels_equal_serial": labels_equal,
-                       "instances_per_tile": {"median": int(np.median(n_instances)), "min": int(min(n_instances)),
-                                              "max": int(max(n_instances))},
-                       "stage_seconds_per_tile_synced_pass": {k: round(v / n_tiles, 5) for k, v in stage.items()
-                                                              if k != "host_enqueue"},
+                                       "util._to_image, H2D and label D2H are in pcie_inclusive, lazy RLE encoding in rle_side (--full)",
+                       "decode_lanes": len(lanes),
                        "host_enqueue_seconds_per_tile": round(stage["host_enqueue"] / (n_tiles * args.steps), 5),
                        "tile_tflop_algorithmic": TILE_TFLOP_ALGORITHMIC},
             "roofline": roof,
         }
+        if args.full:
+            out["config"].update({
+                "pipelined_labels_equal_serial": labels_equal,
+                "instances_per_tile": {"median": int(np.median(n_instances)), "min": int(min(n_instances)), "max": int(max(n_instances))},
+                "stage_seconds_per_tile_synced_pass": {k: round(v / n_tiles, 5) for k, v in stage.items() if k != "host_enqueue"}})
         if not args.no_side:
             out["pcie_inclusive"] = {"value": round(n_pcie * n_tiles / pcie_elapsed, 2), "unit": "tiles/s", "tiles": n_pcie * n_tiles,
                                      "includes": "pinned asynchronous H2D of the raw uint8 tiles (1 MiB each), util._to_image on the "
@@ -1054,7 +1073,10 @@ def main():
             del tiles_u8
             torch.cuda.empty_cache()
             out.update(config_sides(fp8=args.fp8_side))
-        emit(out)
+        if args.full:
+            emit(out)
+        else:
+            print(compact_line(out), flush=True)
     if world > 1 or force_dist:
         dist.destroy_process_group()
 

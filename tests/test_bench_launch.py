@@ -156,3 +156,20 @@ def test_dump_outputs_writes_seeded_float_arrays_under_the_limit(tmp_path):
     with pytest.raises(RuntimeError):
         bench.dump_outputs(str(tmp_path / "f"), {"labels": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32)})
     assert not (tmp_path / "f").exists()
+
+
+def test_plain_run_line_carries_the_contract_fields_without_the_full_run_blocks():
+    """A plain run (no --full) prints compact_line of the contract fields + config: strict JSON, no extras path, no parity or side blocks;
+    --full is accepted next to the other options."""
+    import bench
+    canned = json.load(open(os.path.join(ROOT, "profiles", "r05_bench_line.json")))
+    contract = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")
+    plain = {k: canned[k] for k in contract}
+    plain["config"] = {k: canned["config"][k] for k in ("workload", "tiles_per_step_per_gpu", "encoder_batch", "decode_lanes")}
+    plain["roofline"] = None
+    rec = json.loads(bench.compact_line(plain))
+    assert all(rec[k] == plain[k] for k in contract) and rec["config"] == plain["config"]
+    assert rec["roofline"] is None and rec["cpu_baseline"] is None and "extras" not in rec
+    assert not [k for k in rec if k.startswith(("mask_iou", "pcie", "api_", "train_", "config3", "split16", "fp8", "interactive"))]
+    r = _run(["--dry-run", "--full", "--steps", "1", "--warmup", "0"])
+    assert r.returncode == 0, r.stderr[-2000:]

@@ -1,10 +1,10 @@
 """Turn the rocprofv3 outputs of a measurement run (gpurun_out/final_*) into the committed summaries under profiles/.
 
 Usage: python tools/summarize_profiles.py [round_tag]          (default r01)
-Inputs (written on the GPU box by the commands quoted in profiles/<tag>_bench_kernel_summary.md):
-  gpurun_out/final_bench.log                    python bench.py                          (bench line incl. cpu_baseline)
-  gpurun_out/final_prof/*/*_kernel_stats.csv   rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline
-  gpurun_out/final_fetch, final_write           rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes)
+Inputs (files of the output folder GO below, written by tools/final_measure.sh, the commands quoted in profiles/<tag>_bench_kernel_summary.md):
+  final_bench.log                    python bench.py --full                   (bench line incl. cpu_baseline)
+  final_prof/*/*_kernel_stats.csv    rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline
+  final_fetch, final_write           rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes)
 """
 import csv
 import glob
@@ -73,10 +73,10 @@ def main():
     per_tile = [int(r["Calls"]) for r in rows if "up_fused_kernel" in r["Name"]]
     tiles = per_tile[0] if per_tile else pb["config"]["tiles_per_step_per_gpu"] * (pb["steps"] + pb["warmup"] + 2)
     with open(os.path.join(OUT, f"{TAG}_bench_kernel_summary.md"), "w") as f:
-        f.write(f"# {TAG}: rocprofv3 kernel summary of `python bench.py --no-cpu-baseline --no-side --lanes 1` on one MI355X\n\n")
+        f.write(f"# {TAG}: rocprofv3 kernel summary of `python bench.py --full --no-cpu-baseline --no-side --lanes 1` on one MI355X\n\n")
         f.write(stamp)
         f.write("Command: `rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/final_prof -- python bench.py "
-                "--no-cpu-baseline --no-side --lanes 1` (no side measurements: every launch belongs to the hot path; one decode lane: kernels of different tiles do not overlap, the same order as the "
+                "--full --no-cpu-baseline --no-side --lanes 1` (no side measurements: every launch belongs to the hot path; one decode lane: kernels of different tiles do not overlap, the same order as the "
                 "serial roofline pass of bench.py)\n")
         f.write(f"(bench line of this profiled run: {pb['value']} tiles/s; unprofiled run with cpu_baseline: {bench['value']} "
                 f"tiles/s, `{TAG}_bench_line.json`).\n\n")
@@ -129,7 +129,7 @@ def main():
         json.dump(table, f, indent=1)
     table.pop("_meta")
     with open(os.path.join(OUT, f"{TAG}_pmc_traffic.md"), "w") as f:
-        f.write(f"# {TAG}: HBM traffic from PMC counters (separate rocprofv3 passes of `python bench.py --steps 1 --warmup 1 "
+        f.write(f"# {TAG}: HBM traffic from PMC counters (separate rocprofv3 passes of `python bench.py --full --steps 1 --warmup 1 "
                 "--no-cpu-baseline --no-side`)\n\n")
         f.write(stamp)
         f.write("Commands: `rocprofv3 --kernel-trace --pmc FETCH_SIZE ...` and `rocprofv3 --kernel-trace --pmc WRITE_SIZE ...` "
