@@ -780,6 +780,30 @@ int msam_strict_instance_norm(const float* x, int64_t ldx, int32_t B, int64_t HW
 int msam_strict_resize_bilinear(const float* in, int32_t B, int32_t h, int32_t w, int32_t pitch_h, int32_t pitch_w, int64_t pixel_pitch, int32_t C,
                                 int32_t H2, int32_t W2, float scale_h, float scale_w, int32_t out_nchw, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Object features of micro_sam.object_classification (object_classification.py:20-217; objfeat.hip): per-object means of the
+ * SAM embedding resampled onto the label grid.  A unit = one embedding + the part of the label image it covers.  desc: int64
+ * [U, MSAM_OBJFEAT_DESC] = {label offset (elements), label row pitch, label rows, label cols (the unit's extent; resized pixels whose
+ * nearest source lies past it are padding), embedding offset (floats), embedding row width (pixels), Rh, Rw, offset of the unit's
+ * int32 tables (ly[Rh], y0[Rh], y1[Rh], lx[Rw], x0[Rw], x1[Rw]), offset of its float tables (wy[Rh], wx[Rw]), first pixel of the unit
+ * in the batch's pixel arrays, embedding rows}.  labels int64 (ids >= 0), ids int64 [n_ids] sorted ascending without 0, emb fp32 channel-last
+ * [.., 256].
+ *   gather: keys int64 [pixels of the batch] = object * U + unit (INT64_MAX for background), area int32 [n_ids] (zeroed here);
+ *   accumulate (after a stable sort of the keys: sorted_keys, perm): chunk_start int32 [n_ids + 1] = exclusive prefix of
+ *     ceil(area / K), pix_start int64 [n_ids] = exclusive prefix of area; partial fp64 [max_chunks, 256] (max_chunks >= chunk_start[n_ids]);
+ *   finish: sums fp64 [n_ids, 256] and area_total int64 [n_ids] are running totals over batches (zeroed by the caller); out (may be
+ *     NULL): [n_ids, 257] rows (area, means) in fp64 (out_f64 = 1) or fp32;
+ *   project: index int32 [n] = position of labels[i] in ids, -1 if absent. */
+#define MSAM_OBJFEAT_DESC 12
+int msam_objfeat_gather(const int64_t* labels, const int64_t* desc, int32_t U, int32_t max_pixels, const int32_t* itab,
+                        const int64_t* ids, int32_t n_ids, int64_t* keys, int32_t* area, void* stream);
+int msam_objfeat_accumulate(const float* emb, const int64_t* desc, int32_t U, const int32_t* itab, const float* ftab,
+                            const int64_t* sorted_keys, const int64_t* perm, const int32_t* chunk_start, const int64_t* pix_start,
+                            const int32_t* area, int32_t n_ids, int32_t K, int32_t max_chunks, double* partial, void* stream);
+int msam_objfeat_finish(const double* partial, const int32_t* chunk_start, const int32_t* area, int32_t n_ids, double* sums,
+                        int64_t* area_total, int32_t out_f64, void* out, void* stream);
+int msam_objfeat_project(const int64_t* labels, int64_t n, const int64_t* ids, int32_t n_ids, int32_t* index, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -246,6 +246,10 @@ _PROTOS = {
     "msam_split16_i2t_block": (_i32, [C.POINTER(SI2TParams), _vp, _i64, _vp]),
     "msam_strict_instance_norm": (_i32, [_vp, _i64, _i32, _i64, _i32, _f32, _vp, _vp, _i64, _vp]),
     "msam_strict_resize_bilinear": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _vp]),
+    "msam_objfeat_gather": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "msam_objfeat_accumulate": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "msam_objfeat_finish": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "msam_objfeat_project": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp]),
 }
 OPTIONAL = set()
 

@@ -578,6 +578,92 @@ def slice_overlaps(labels: torch.Tensor) -> np.ndarray:
     return e[np.lexsort((e[:, 1], e[:, 0]))] if n_edges else e.reshape(0, 3)
 
 
+
+OBJFEAT_DESC = 12            # include/msam_hip.h MSAM_OBJFEAT_DESC
+(OF_LAB_OFF, OF_LAB_LD, OF_LAB_H, OF_LAB_W, OF_EMB_OFF, OF_EMB_W, OF_RH, OF_RW, OF_ITAB, OF_FTAB, OF_PIX, OF_EMB_H) = range(OBJFEAT_DESC)
+
+
+def _objfeat_check_units(desc: np.ndarray, itab: np.ndarray, ftab: np.ndarray, n_labels: int, n_emb: int) -> int:
+    """Every address the object-feature kernels form from a unit descriptor stays inside its buffer; returns the batch's pixels."""
+    if desc.ndim != 2 or desc.shape[1] != OBJFEAT_DESC or not 1 <= desc.shape[0] <= 65535 or desc.dtype != np.int64:
+        raise ValueError("objfeat: desc must be int64 [U, 12] with 1 <= U <= 65535")
+    if itab.dtype != np.int32 or ftab.dtype != np.float32 or itab.ndim != 1 or ftab.ndim != 1:
+        raise ValueError("objfeat: itab must be int32 [n], ftab float32 [n]")
+    pix = 0
+    for d in desc.tolist():
+        lo, ld, lh, lw, eo, ew, rh, rw, it, ft, p0, eh = d
+        if min(lh, lw, ew, eh, rh, rw) < 1 or ld < lw or lo < 0 or lo + (lh - 1) * ld + lw > n_labels:
+            raise ValueError(f"objfeat: unit {d} addresses labels outside [0, {n_labels})")
+        if eo < 0 or eo % 4 or eo + eh * ew * 256 > n_emb:
+            raise ValueError(f"objfeat: unit {d} addresses the embedding outside [0, {n_emb})")
+        if it < 0 or it + 3 * (rh + rw) > itab.size or ft < 0 or ft + rh + rw > ftab.size or p0 != pix or rh * rw >= 1 << 31:
+            raise ValueError(f"objfeat: unit {d} has bad table offsets or pixel start")
+        t = itab[it: it + 3 * (rh + rw)]
+        ly, y01, lx, x01 = t[:rh], t[rh: 3 * rh], t[3 * rh: 3 * rh + rw], t[3 * rh + rw:]
+        if ly.min() < 0 or lx.min() < 0 or y01.min() < 0 or y01.max() >= eh or x01.min() < 0 or x01.max() >= ew:
+            raise ValueError(f"objfeat: unit {d} has resize tables outside its embedding")
+        pix += rh * rw
+    return pix
+
+
+def objfeat_accumulate_batch(labels: torch.Tensor, ids: torch.Tensor, emb: torch.Tensor, desc: np.ndarray, itab: np.ndarray,
+                             ftab: np.ndarray, sums: torch.Tensor, area_total: torch.Tensor, out: Optional[torch.Tensor] = None,
+                             chunk: int = 128) -> None:
+    """One batch of object-feature units (include/msam_hip.h msam_objfeat_*): gather the resized labels (sort key object * U + unit),
+    stable-sort the keys (torch.sort: plumbing), accumulate every object's resampled embedding in fp64 chunks of ``chunk`` pixels and
+    add them, in chunk order, to the running ``sums`` fp64 [N, 256] / ``area_total`` int64 [N].  ``out`` ([N, 257] fp32 or fp64): the
+    (area, means) rows after this batch.  labels int64 (any shape, contiguous), ids int64 [N] sorted without 0, emb fp32 flat channel-last
+    units; desc / itab / ftab host arrays, checked here against every buffer before anything is launched."""
+    dev = labels.device
+    n = ids.numel()
+    for t, dt in ((labels, torch.int64), (ids, torch.int64), (emb, torch.float32), (sums, torch.float64), (area_total, torch.int64)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"objfeat: expected a contiguous {dt} tensor on {dev}, got {t.dtype} on {t.device}")
+    if n < 1 or n >= 1 << 31 or ids.dim() != 1 or tuple(sums.shape) != (n, 256) or tuple(area_total.shape) != (n,):
+        raise ValueError("objfeat: ids [N] (1 <= N < 2^31), sums [N, 256], area_total [N]")
+    if out is not None and (tuple(out.shape) != (n, 257) or out.dtype not in (torch.float32, torch.float64) or not out.is_contiguous()
+                            or out.device != dev):
+        raise ValueError("objfeat: out must be a contiguous [N, 257] fp32 / fp64 tensor")
+    if not 1 <= chunk <= 1 << 20:
+        raise ValueError("objfeat: chunk must be in [1, 2^20]")
+    pixels = _objfeat_check_units(desc, itab, ftab, labels.numel(), emb.numel())
+    u = desc.shape[0]
+    max_pixels = int((desc[:, OF_RH] * desc[:, OF_RW]).max())
+    desc_d, itab_d, ftab_d = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (desc, itab, ftab))
+    keys = torch.empty((pixels,), dtype=torch.int64, device=dev)
+    area = torch.empty((n,), dtype=torch.int32, device=dev)
+    lib, stream = _lib.load(), _lib.stream_ptr()
+    _lib.check(lib.msam_objfeat_gather(labels.data_ptr(), desc_d.data_ptr(), u, max_pixels, itab_d.data_ptr(), ids.data_ptr(), n,
+                                       keys.data_ptr(), area.data_ptr(), stream), "msam_objfeat_gather")
+    sorted_keys, perm = torch.sort(keys, stable=True)
+    area64 = area.to(torch.int64)
+    pix_start = (torch.cumsum(area64, 0) - area64).contiguous()
+    chunk_start = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+    chunk_start[1:] = torch.cumsum((area64 + chunk - 1) // chunk, 0)
+    chunk_start = chunk_start.to(torch.int32)
+    max_chunks = pixels // chunk + min(n, pixels) + 1          # >= sum ceil(area / chunk) for any split of the pixels
+    partial = torch.empty((max_chunks, 256), dtype=torch.float64, device=dev)
+    _lib.check(lib.msam_objfeat_accumulate(emb.data_ptr(), desc_d.data_ptr(), u, itab_d.data_ptr(), ftab_d.data_ptr(),
+                                           sorted_keys.data_ptr(), perm.data_ptr(), chunk_start.data_ptr(), pix_start.data_ptr(),
+                                           area.data_ptr(), n, chunk, max_chunks, partial.data_ptr(), stream), "msam_objfeat_accumulate")
+    _lib.check(lib.msam_objfeat_finish(partial.data_ptr(), chunk_start.data_ptr(), area.data_ptr(), n, sums.data_ptr(),
+                                       area_total.data_ptr(), int(out is not None and out.dtype == torch.float64),
+                                       None if out is None else out.data_ptr(), stream), "msam_objfeat_finish")
+
+
+def objfeat_project(labels: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """Position of every label in the sorted int64 id table ``ids`` (-1 where absent): int32, the shape of ``labels`` (int64)."""
+    if labels.dtype != torch.int64 or ids.dtype != torch.int64 or ids.dim() != 1 or ids.device != labels.device or ids.numel() >= 1 << 31:
+        raise ValueError("objfeat_project: int64 labels and a 1-d int64 id table on the same device")
+    labels, ids = labels.contiguous(), ids.contiguous()
+    index = torch.empty(labels.shape, dtype=torch.int32, device=labels.device)
+    if labels.numel() == 0:
+        return index
+    _lib.check(_lib.load().msam_objfeat_project(labels.data_ptr(), labels.numel(), ids.data_ptr() if ids.numel() else None, ids.numel(),
+                                                index.data_ptr(), _lib.stream_ptr()), "msam_objfeat_project")
+    return index
+
+
 def component_sizes(roots: torch.Tensor):
     """(sizes int32 [n] keyed by root index, bg_count int32[1]) for roots int32 [n] (-1 = background)."""
     n = roots.numel()
