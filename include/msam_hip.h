@@ -77,10 +77,11 @@ typedef struct {
     int32_t a_dtype;
     const float* row_scale; const float* col_scale;        /* fp32 [M], [N] */
     /* split_k > 1 (128 x 128-tile bf16 / fp16 path): the contraction is cut into split_k slices, one workgroup per (tile, slice),
-     * partial tiles are added into `out` with fp32 atomics (out is zeroed first).  For products with a small output and a very long
-     * contraction (the weight gradients of fine-tuning: dW = dY^T X over all rows).  Plain fp32 output with ldc == N, no bias /
-     * table / residual / activation; K % (64 * split_k) == 0.  0 / 1 = off.  The slices meet in fp32 atomics: the result is NOT
-     * bit-reproducible from run to run (order of the additions; training gradients only - no inference path sets it). */
+     * each slice's partial tile goes to a library-owned workspace and a second pass adds the slices in slice order into `out`
+     * (overwritten): the same bits on every run.  For products with a small output and a very long contraction (the weight
+     * gradients of fine-tuning: dW = dY^T X over all rows).  Plain fp32 output with ldc == N, no bias / table / residual /
+     * activation; K % (64 * split_k) == 0.  0 / 1 = off.  The workspace is shared with msam_cast_transpose and
+     * msam_layernorm_backward: call these from one stream at a time. */
     int32_t split_k;
     /* ln_mode 1 only (the mask decoder's token side): the normalised row is ALSO written as 16-bit operand copies for the next
      * products - ln_out_a [M,256] = round16(y + ln_add[row]) (ln_add fp32 [M,256] or NULL), ln_out_b [M,256] = round16(y); the 16-bit
@@ -307,7 +308,8 @@ int msam_labels_from_masks(const uint32_t* bits, const int32_t* order, int32_t K
 /* ---- fine-tuning (micro_sam/training/sam_trainer.py:131-425, trainable_sam.py:12-114): backward
  * kernels of the mask decoder's non-GEMM pieces (the GEMMs run msam_gemm_bf16 in both directions: dX = dY W, dW = dY^T X).
  * msam_layernorm_backward: x, dy, dx fp32 [rows, dim] (dim 64 / 128 / 256; 768 / 1024 / 1280 for the encoder), dweight / dbias fp32 [dim] ACCUMULATED
- *   (zero them first).
+ *   (zero them first); the workgroups' sums are added in a fixed order (the same bits on every run) through library-owned workspaces
+ *   shared with split-K msam_gemm_bf16 and msam_cast_transpose: call these from one stream at a time.
  * msam_attention_forward / backward: softmax(scale q k^T) v for q fp32 [BH, Nq, D], k / v fp32 [BH, Nk, D], D = 16 or 32;
  *   lse fp32 [BH, Nq] (log-sum-exp of the scaled scores, saved for the backward pass), delta: workspace fp32 [BH, Nq]. */
 int msam_layernorm_backward(const float* x, const float* weight, const float* dy, float eps, int64_t rows, int32_t dim,
@@ -337,7 +339,9 @@ int msam_relpos_attention_backward(const float* q, const float* k, const float* 
 
 /* Operands of a weight gradient in one pass (training; micro_sam_amd/training/functional.py _Linear): x [M, K] fp32 or bf16 (x_dtype
  * MSAM_F32 / MSAM_BF16), row stride ldx elements -> out16 [M, K] bf16 copy, outT [K, M] bf16 transpose, colsum [K] fp32 column sums
- * ADDED to the caller's buffer (atomics; the bias gradient).  Any of the three outputs may be NULL.  K % 4 == 0, ldx % 4 == 0.
+ * ADDED to what the caller's buffer holds (the bias gradient; the blocks of 64 rows are added in a fixed order: the same bits on every
+ * run).  Any of the three outputs may be NULL.  K % 4 == 0, ldx % 4 == 0, M <= 4 194 240.  The column sums use library-owned
+ * workspaces shared with split-K msam_gemm_bf16 and msam_layernorm_backward: call these from one stream at a time.
  * Replaces torch's cast + strided transpose copy + sum launches behind the reference's autograd (torch.nn.functional.linear backward). */
 int msam_cast_transpose(const void* x, int32_t x_dtype, int64_t M, int32_t K, int64_t ldx, void* out16, void* outT, float* colsum,
                         void* stream);

@@ -11,7 +11,7 @@
 #include "../../include/msam_hip.h"
 
 float* msam_det_workspace(size_t floats, int slot);                                           // train.hip: library-owned workspaces of the fixed-order reductions
-void msam_det_reduce(const float* parts, int nparts, long n, float* out, int accumulate, void* stream);
+int msam_det_reduce(const float* parts, int nparts, long n, float* out, int accumulate, void* stream);
 
 namespace {
 
@@ -1418,8 +1418,8 @@ extern "C" int msam_gemm_bf16(const msam_gemm_t* p, void* stream) {
     }
     if (p->split_k > 1) {
         // split-K (training: dW = dY^T X contracts over hundreds of thousands of rows into a 128 x 256 tile or two - a handful of
-        // workgroups would walk the whole contraction one after the other): split_k slices of K, one workgroup per (tile, slice), fp32
-        // atomic accumulation into the zeroed output
+        // workgroups would walk the whole contraction one after the other): split_k slices of K, one workgroup per (tile, slice), each
+        // slice's tile to its part of a workspace, the parts added in slice order (msam_det_reduce)
         if (p->out_mode != 0 || p->out_dtype != MSAM_F32 || p->bias || p->table || p->resid || p->act || p->ldc != p->N ||
             p->K % (p->split_k * BK)) {
             msam_set_error("msam_gemm_bf16(split_k): plain fp32 output with ldc == N, no bias / table / residual / activation, K % (split_k * 64) == 0");
@@ -1433,7 +1433,10 @@ extern "C" int msam_gemm_bf16(const msam_gemm_t* p, void* stream) {
                                     (const u16*)p->W, (long)p->ldw, p->M, p->N, p->K, e);
         else hipLaunchKernelGGL(gemm_kernel<false>, dim3(tiles, p->split_k), dim3(256), 0, s, (const u16*)p->A, (long)p->lda,
                                 (const u16*)p->W, (long)p->ldw, p->M, p->N, p->K, e);
-        msam_det_reduce(parts, p->split_k, (long)p->M * p->N, (float*)p->out, 0, stream);       // out = slice 0 + slice 1 + ... in that order
+        if (msam_det_reduce(parts, p->split_k, (long)p->M * p->N, (float*)p->out, 0, stream)) {      // out = slice 0 + slice 1 + ... in that order
+            msam_set_error("msam_gemm_bf16(split_k): cannot allocate the reduction workspace");
+            return 2;
+        }
         return msam_check_launch("msam_gemm_bf16(split_k)");
     }
     if (prof) {

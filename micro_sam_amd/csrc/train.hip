@@ -2,7 +2,7 @@
 // trainable_sam.py:12-114): LayerNorm backward, and softmax attention forward / backward for the
 // decoder's shapes (8 heads, head dim 16 or 32, <= 16 prompt tokens on one side and 4096 image tokens or <= 16 tokens on the
 // other).  All fp32: these are the small, latency-bound pieces around the GEMMs (which run on the MFMA GEMM kernel in both
-// directions: dX = dY W, dW = dY^T X).  No atomics on the data path except the per-column parameter-gradient sums.
+// directions: dX = dY W, dW = dY^T X).  No atomics: the parameter-gradient sums over workgroups are added in a fixed order.
 #include "common.h"
 #include "../../include/msam_hip.h"
 
@@ -61,11 +61,12 @@ const float* msam_det_reduce_tree(const float* parts, int* nparts, long n, void*
     }
     return parts;
 }
-// out[i] (+)= the sum of the parts, in a fixed order
-void msam_det_reduce(const float* parts, int nparts, long n, float* out, int accumulate, void* stream) {
+// out[i] (+)= the sum of the parts, in a fixed order.  Returns 0, or 2 when the tree's workspace cannot be allocated (out is then unwritten).
+int msam_det_reduce(const float* parts, int nparts, long n, float* out, int accumulate, void* stream) {
     parts = msam_det_reduce_tree(parts, &nparts, n, stream);
-    if (!parts) return;
+    if (!parts) return 2;
     hipLaunchKernelGGL(det_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, parts, nparts, n, out, accumulate);
+    return 0;
 }
 
 namespace {
@@ -442,7 +443,7 @@ __global__ __launch_bounds__(128) void relpos_bwd_kv_kernel(const float* __restr
 //   out16 [M, K]  bf16 copy (optional)            - coalesced 8-byte writes,
 //   outT  [K, M]  bf16 transpose (optional)       - through a padded LDS tile, 8-byte writes along M,
 //   colsum        fp32 column sums (optional)     - per-workgroup partial sums (fixed order inside the workgroup) to part [gridDim.y][K]; the
-//                                                   launcher adds the row blocks in order (msam_det_reduce) INTO the caller's zeroed vector.
+//                                                   launcher adds the row blocks in order (msam_det_reduce) INTO the caller's vector.
 // The unfused form was three to four torch launches per operand (cast, strided transpose copy at 0.5 TB/s, sum): 30 % of a fine-tuning
 // step's device time (profiles/r03_experiments.md section 8).  K % 4 == 0, ldx % 4 == 0; M arbitrary.
 template <bool SRC16>
@@ -639,6 +640,10 @@ extern "C" int msam_cast_transpose(const void* x, int32_t x_dtype, int64_t M, in
     else
         hipLaunchKernelGGL(cast_transpose_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, (long)M, K, (long)ldx, (unsigned short*)out16,
                            (unsigned short*)outT, part);
-    if (colsum) msam_det_reduce(part, (int)grid.y, K, colsum, 1, stream);       // colsum += row block 0 + row block 1 + ... (the caller zeroes it)
+    // colsum += row block 0 + row block 1 + ... (added to what the caller's buffer holds)
+    if (colsum && msam_det_reduce(part, (int)grid.y, K, colsum, 1, stream)) {
+        msam_set_error("msam_cast_transpose: cannot allocate the reduction workspace");
+        return 2;
+    }
     return msam_check_launch("msam_cast_transpose");
 }

@@ -28,7 +28,8 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
          ln_b: Optional[torch.Tensor] = None, ln_eps: float = 1e-5, split_k: int = 0) -> torch.Tensor:
     """act(LN(a[M,K] @ w[N,K]^T + bias + table[row % rows, :table_cols] + resid)); a, w bf16.
     ln_mode 1: LayerNorm over the row (N == 256); 2: LayerNorm over 64-column groups + GELU.
-    split_k > 1: the contraction in split_k slices accumulated with fp32 atomics (plain fp32 output, K % (64 * split_k) == 0)."""
+    split_k > 1: the contraction in split_k slices added in slice order, the same bits on every run (plain fp32 output,
+    K % (64 * split_k) == 0; a library-owned workspace: one stream at a time)."""
     _lib.require_gpu()
     assert a.dtype == w.dtype and a.dtype in (torch.bfloat16, torch.float16) and a.is_contiguous() and w.is_contiguous()
     M, K = a.shape

@@ -38,7 +38,8 @@ def _mm_nt(a16: torch.Tensor, b16: torch.Tensor, bias: torch.Tensor = None, n: i
     multiple of 64 and N to a multiple of 128 (the kernel's tile constraints; ``n`` = valid rows of an operand padded beforehand), M is
     arbitrary.  A small output with a very long
     contraction (the weight gradients: M, N <= a few hundred, K = all rows of the batch) is cut into slices of K that run on separate
-    workgroups and accumulate with fp32 atomics (``split_k``) - two workgroups would otherwise walk the whole contraction serially."""
+    workgroups and are added in slice order (``split_k``; the same bits on every run) - two workgroups would otherwise walk the whole
+    contraction serially."""
     M, K = a16.shape
     N = b16.shape[0] if n is None else n             # n: rows of b16 that count (b16 already zero-padded to the tile, _weight16)
     K = max(K, b16.shape[1])

@@ -30,33 +30,52 @@ def dice_loss_per_channel(prediction: torch.Tensor, target: torch.Tensor, eps: f
     return 1.0 - 2.0 * num / den.clamp(min=eps)
 
 
+def _fired_anywhere(fired: List[bool], device) -> List[bool]:
+    """Per-parameter "has a gradient" flags OR-ed over the ranks (one small SUM all-reduce; every rank must call it at the same point of
+    its sequence of collectives)."""
+    flags = torch.tensor([int(f) for f in fired], dtype=torch.int32, device=device)
+    dist.all_reduce(flags, op=dist.ReduceOp.SUM)
+    return [c > 0 for c in flags.tolist()]
+
+
 def all_reduce_gradients(parameters: Iterable[torch.nn.Parameter], bucket_bytes: int = 64 << 20) -> int:
     """Average the gradients over the ranks of the default process group: flat fp32 buckets of ``bucket_bytes`` (64 MiB: a few
-    large RCCL all-reduces over xGMI instead of one per tensor), in place.  Returns the number of bytes reduced."""
+    large RCCL all-reduces over xGMI instead of one per tensor), in place.  Returns the number of bytes reduced.
+
+    DDP semantics: a parameter that has a gradient on ANY rank gets the average on every rank, a rank without one contributing zeros
+    (its ``.grad`` is created); a parameter without a gradient on every rank keeps ``.grad = None``.  The ranks agree on that first
+    (one flag per parameter), so they all build the same buckets in the same order."""
     from ..parallel import collectives_active
     if not collectives_active():
         return 0
     world = dist.get_world_size()
-    grads = [p.grad for p in parameters if p.requires_grad and p.grad is not None]
+    params = [p for p in parameters if p.requires_grad]
+    if not params:
+        return 0
+    fired = _fired_anywhere([p.grad is not None for p in params], params[0].device)
     total, bucket, size = 0, [], 0
 
     def flush():
         nonlocal bucket, size, total
         if not bucket:
             return
-        flat = torch.cat([g.reshape(-1).float() for g in bucket])
+        flat = torch.cat([g.reshape(-1).float() for _, g in bucket])
         dist.all_reduce(flat, op=dist.ReduceOp.SUM)
         flat /= world
         off = 0
-        for g in bucket:
+        for p, g in bucket:
             n = g.numel()
             g.copy_(flat[off:off + n].reshape(g.shape))
+            if p.grad is None:
+                p.grad = g
             off += n
         total += flat.numel() * 4
         bucket, size = [], 0
-    for g in grads:
-        bucket.append(g)
-        size += g.numel() * 4
+    for p, f in zip(params, fired):
+        if not f:
+            continue
+        bucket.append((p, p.grad if p.grad is not None else torch.zeros_like(p.detach())))
+        size += p.numel() * 4
         if size >= bucket_bytes:
             flush()
     flush()
@@ -69,10 +88,16 @@ class GradientBuckets:
 
     The parameters' ``.grad`` tensors ARE slices of flat fp32 buckets (``bucket_bytes`` each; parameters in reverse registration order =
     roughly the order in which backward finishes them): no ``cat`` before the all-reduce and no copy back after it (the two extra passes
-    over the gradients of the round-4 form).  A post-accumulate hook counts a bucket's finished gradients; the last one starts that
-    bucket's asynchronous all-reduce - on a communication stream that waits for the producing stream at that point - while backward
-    continues with the layers in front of it.  ``finish()`` starts whatever is left (parameters that got no gradient in this step),
-    waits, and divides by the world size.  ``zero()`` replaces ``optimizer.zero_grad()`` (which would drop the views)."""
+    over the gradients of the round-4 form).  A post-accumulate hook counts a bucket's finished gradients; the last one marks the bucket
+    ready and starts the asynchronous all-reduces of the ready buckets at the launch cursor - on a communication stream that waits for
+    the producing stream at that point - while backward continues with the layers in front of it.  ``finish()`` starts whatever is left (parameters that got no gradient in this step),
+    waits, and divides by the world size.  ``zero()`` replaces ``optimizer.zero_grad()`` (which would drop the views).
+
+    Collectives are matched by call order, so every rank starts the buckets in bucket order: a completed bucket waits for the ones in
+    front of it (a parameter may get a gradient on some ranks only - a data-dependent graph - and its bucket then completes on those
+    ranks only, and starts in ``finish()``).  A parameter without a gradient on a rank contributes its zeroed view, as under DDP.
+    ``finish()`` then exchanges one "got a gradient" flag per parameter, at the same point on every rank, and gives ``.grad = None``
+    only to the parameters that got none on any rank."""
 
     def __init__(self, parameters: Iterable[torch.nn.Parameter], bucket_bytes: int = 64 << 20) -> None:
         self.params = [p for p in parameters if p.requires_grad]
@@ -89,6 +114,7 @@ class GradientBuckets:
             self._make_bucket(cur)
         self._comm = None
         self._handles = []
+        self._next = 0                                               # the launch cursor: buckets [0, _next) are started
         for b in self.buckets:
             for q in b["params"]:
                 b["hooks"].append(q.register_post_accumulate_grad_hook(lambda _p, b=b: self._ready(b, _p)))
@@ -100,7 +126,7 @@ class GradientBuckets:
         for q in params:
             views.append(flat[off:off + q.numel()].view(q.shape))
             off += q.numel()
-        self.buckets.append({"flat": flat, "params": list(params), "views": views, "ready": 0, "launched": False, "hooks": [], "fired": set()})
+        self.buckets.append({"flat": flat, "params": list(params), "views": views, "ready": False, "launched": False, "hooks": [], "fired": set()})
         self._attach(self.buckets[-1])
 
     @staticmethod
@@ -112,10 +138,11 @@ class GradientBuckets:
     def zero(self) -> None:
         for b in self.buckets:
             b["flat"].zero_()
-            b["ready"], b["launched"] = 0, False
+            b["ready"], b["launched"] = False, False
             b["fired"].clear()
             self._attach(b)
         self._handles = []
+        self._next = 0
 
     def _launch(self, b) -> None:
         b["launched"] = True
@@ -133,19 +160,23 @@ class GradientBuckets:
         else:
             self._handles.append((dist.all_reduce(flat, op=dist.ReduceOp.SUM, async_op=True), b))
 
-    def _ready(self, b, p=None) -> None:
-        b["ready"] += 1
-        if p is not None:
-            b["fired"].add(id(p))
-        if b["ready"] == len(b["params"]) and not b["launched"]:
-            self._launch(b)
+    def _ready(self, b, p) -> None:
+        b["fired"].add(id(p))
+        if len(b["fired"]) == len(b["params"]):
+            b["ready"] = True
+            while self._next < len(self.buckets) and self.buckets[self._next]["ready"]:     # in bucket order on every rank
+                self._launch(self.buckets[self._next])
+                self._next += 1
 
     def finish(self) -> int:
         """Start the buckets backward did not complete, wait for all of them, average.  Returns the bytes reduced."""
         total = 0
-        for b in self.buckets:
-            if not b["launched"]:
-                self._launch(b)
+        for b in self.buckets[self._next:]:
+            self._launch(b)
+        self._next = len(self.buckets)
+        # the one fixed point of the flag exchange: after the last bucket's all-reduce on every rank
+        fired = _fired_anywhere([id(q) in b["fired"] for b in self.buckets for q in b["params"]], self.buckets[0]["flat"].device) \
+            if self.buckets else []
         for work, b in self._handles:
             work.wait()
             if b["flat"].is_cuda:
@@ -153,13 +184,13 @@ class GradientBuckets:
             b["flat"].div_(self.world)
             total += b["flat"].numel() * 4
         self._handles = []
-        # a parameter that received no gradient in this step has `.grad = None` for the optimizer, as without the buckets (its zero-filled
-        # view would make AdamW decay it and move its moments: the overlapped and the plain path must produce the same update - ADVICE r5);
-        # `zero()` attaches the views again
-        for b in self.buckets:
-            for q in b["params"]:
-                if id(q) not in b["fired"]:
-                    q.grad = None
+        # a parameter that received no gradient in this step on ANY rank has `.grad = None` for the optimizer, as without the buckets (its
+        # zero-filled view would make AdamW decay it and move its moments: the overlapped and the plain path must produce the same update -
+        # ADVICE r5); one that got a gradient on some rank keeps the average on every rank (DDP).  `zero()` attaches the views again
+        qs = [q for b in self.buckets for q in b["params"]]
+        for q, f in zip(qs, fired):
+            if not f:
+                q.grad = None
         return total
 
     def remove(self) -> None:

@@ -657,7 +657,7 @@ def test_gemm_fp8_vs_torch(env, M, N, K, mode):
 
 def test_gemm_split_k_matches_the_plain_product():
     """msam_gemm_t.split_k: a small output with a very long contraction (fine-tuning's weight gradients dW = dY^T X) cut into slices
-    that accumulate with fp32 atomics == the same product on one workgroup chain (up to the summation order)."""
+    whose partial tiles are added in slice order == the same product on one workgroup chain (up to the summation order)."""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     from micro_sam_amd import ops

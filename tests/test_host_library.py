@@ -249,3 +249,40 @@ def test_amg_generate_labels_edge_cases(lib, case):
     state = {"crop_list": [data], "crop_boxes": [[0, 0, W, H]], "original_size": (H, W)}
     seg = np.asarray(PR.amg_generate(state, with_background=bool(wb)))
     assert np.array_equal(labels.astype(np.int64), seg.astype(np.int64)), case
+
+
+def test_fixed_order_reductions_exact_through_the_abi(lib):
+    """The fixed-order reductions (train.hip msam_det_reduce / msam_det_reduce_tree: groups of 32 parts per level, alternating halves of
+    one workspace) at part counts that cross the tree's thresholds, on small integers: every fp32 partial sum is exact in any order, so
+    the results EQUAL the float64 sums.  The column sums and dbias are added onto a non-zero start.  (tests/test_gpu_det_reductions.py
+    runs the same checks and the random-data bounds on the device.)"""
+    from micro_sam_amd import _lib as L
+    rng = np.random.default_rng(11)
+    for M in (2048, 2049, 65537, 4194240):                       # 32, 33, 1025, 65 535 parts: 0 to 3 tree levels
+        K = 4
+        x = rng.integers(-2, 3, (M, K)).astype(np.float32)
+        cs = rng.integers(-1000, 1001, K).astype(np.float32)
+        want = cs.astype(np.float64) + x.astype(np.float64).sum(0)
+        assert lib.msam_cast_transpose(_p(x), F32, C.c_int64(M), K, C.c_int64(K), None, None, _p(cs), None) == 0, _err(lib)
+        assert np.array_equal(cs.astype(np.float64), want), M
+    for rows, dim in ((129, 64), (4097, 64), (100000, 64)):         # 33, 1025, 2048 parts
+        xs = rng.standard_normal((rows, dim)).astype(np.float32)
+        w = (rng.standard_normal(dim) * 0.3 + 1).astype(np.float32)
+        dy = rng.integers(-4, 5, (rows, dim)).astype(np.float32)
+        dx = np.zeros((rows, dim), np.float32)
+        dw, db = np.zeros(dim, np.float32), rng.integers(-500, 501, dim).astype(np.float32)
+        want = db.astype(np.float64) + dy.astype(np.float64).sum(0)
+        assert lib.msam_layernorm_backward(_p(xs), _p(w), _p(dy), C.c_float(1e-6), C.c_int64(rows), dim, _p(dx), _p(dw), _p(db), None) == 0, _err(lib)
+        assert np.array_equal(db.astype(np.float64), want), rows
+    for split in (33, 64):                                          # 33 parts: one tree level; 64 parts: two groups of 32
+        K = 64 * split * 2
+        a = torch.from_numpy(rng.integers(-3, 4, (128, K)).astype(np.float32)).to(torch.bfloat16)
+        w = torch.from_numpy(rng.integers(-3, 4, (128, K)).astype(np.float32)).to(torch.bfloat16)
+        A_, W_ = (t.view(torch.int16).numpy().view(np.uint16).copy() for t in (a, w))
+        out = np.full((128, 128), np.nan, np.float32)
+        p = L.GemmParams()
+        for k, v in dict(A=A_.ctypes.data, W=W_.ctypes.data, M=128, N=128, K=K, lda=K, ldw=K, ldc=128, out=out.ctypes.data, out_dtype=F32,
+                         split_k=split).items():
+            setattr(p, k, v)
+        assert lib.msam_gemm_bf16(C.byref(p), None) == 0, _err(lib)
+        assert np.array_equal(out.astype(np.float64), (a.double() @ w.double().t()).numpy()), split
