@@ -26,6 +26,9 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from .ops import _home, _need, _t
+
+_F32 = torch.float32
 
 GRID, PROMPT_DIM, WINDOW = 64, 256, 14
 T = GRID * GRID
@@ -145,6 +148,8 @@ def weight_scale(w: torch.Tensor) -> float:
 def weight_pairs(w: torch.Tensor, permute: bool) -> torch.Tensor:
     """``w`` [N, K] as fp16 pairs in the split16 kernels' LDS tile layout (msam_split16_prepare_pairs), scaled by ``weight_scale(w)``; cached with
     the scale."""
+    _t("w", w, _F32, (None, None), _home("w", w))
+
     def make():
         t = torch.empty((w.shape[0], 2 * w.shape[1]), dtype=torch.float16, device=w.device)
         _lib.check(_lib.load().msam_split16_prepare_pairs(w.data_ptr(), w.shape[0], w.shape[1], weight_scale(w), 1 if permute else 0, t.data_ptr(),
@@ -168,12 +173,28 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
          a2_cols: int = 0) -> torch.Tensor:
     """``act((a + a2[row % a2_rows]) @ w.T + bias) + res[row % res_rows]`` (fp32).  ``a``: [M, K] rows (``rows`` / ``lda`` /
     ``a_offset`` address a strided row set inside a larger buffer: the output tokens of the two-way transformer); ``a2_cols``: ``a2``
-    is added for the first ``a2_cols`` output columns only (two projections of one input in one launch)."""
-    K = w.shape[1]
+    is added for the first ``a2_cols`` output columns only (two projections of one input in one launch).  Every tensor is fp32 on one
+    device; ``a``, ``a2``, ``w``, ``res`` and ``out`` may be 2-d views with contiguous rows (their row strides are handed over)."""
+    dev = _home("w", w)
+    _t("w", w, _F32, (None, None), dev, rows=True)
+    N, K = w.shape
+    _t("a", a, _F32, (None, K), dev, rows=True)
     M = a.shape[0] if rows is None else rows
-    N = w.shape[0]
+    if rows is not None or lda is not None or a_offset:
+        ld = a.stride(0) if lda is None else lda
+        _need(a.is_contiguous() and M >= 1 and ld >= 0 and a_offset >= 0 and (M - 1) * ld + a_offset + K <= a.numel(),
+              f"a: rows = {M}, lda = {ld}, a_offset = {a_offset} address elements outside a {list(a.shape)}")
+    if bias is not None:
+        _t("bias", bias, _F32, (N,), dev)
+    if a2 is not None:
+        _t("a2", a2, _F32, (None, K), dev, rows=True)
+        _need(a2_rows >= 0 and a2.shape[0] >= (a2_rows or M), f"a2 has {a2.shape[0]} rows, the kernel reads {a2_rows or M}")
+    if res is not None:
+        _t("res", res, _F32, (None, N), dev, rows=True)
+        _need(res_rows >= 0 and res.shape[0] >= (res_rows or M), f"res has {res.shape[0]} rows, the kernel reads {res_rows or M}")
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=w.device)
+    _t("out", out, _F32, (M, N), dev, rows=True)
     p = _lib.SGemmParams()
     p.A, p.lda = a.data_ptr() + 4 * a_offset, (a.stride(0) if lda is None else lda)
     if a2 is not None:
@@ -192,10 +213,18 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
 
 def layer_norm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float, out: Optional[torch.Tensor] = None, gelu: bool = False,
                nchw_hw: int = 0, rows: Optional[int] = None, dim: Optional[int] = None) -> torch.Tensor:
+    dev = _home("x", x)
+    _t("x", x, _F32, None, dev)
     rows = x.shape[0] if rows is None else rows
     dim = x.shape[1] if dim is None else dim
+    _need(rows >= 1 and dim >= 1 and rows * dim == x.numel(), f"x {list(x.shape)} does not hold rows = {rows} of dim = {dim}")
+    _t("w", w, _F32, (dim,), dev)
+    _t("b", b, _F32, (dim,), dev)
+    _need(nchw_hw >= 0 and (not nchw_hw or rows % nchw_hw == 0), f"nchw_hw = {nchw_hw} must divide rows = {rows}")
     if out is None:
         out = torch.empty_like(x)
+    _t("out", out, _F32, None, dev)
+    _need(out.numel() == x.numel(), f"out {list(out.shape)} must hold the {x.numel()} elements of x")
     _lib.check(_lib.load().msam_strict_layernorm(x.data_ptr(), w.data_ptr(), b.data_ptr(), float(eps), rows, dim, out.data_ptr(),
                                                  1 if gelu else 0, nchw_hw, _lib.stream_ptr()), "msam_strict_layernorm")
     return out
@@ -204,6 +233,10 @@ def layer_norm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float, ou
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, H: int, Nq: int, Nk: int, D: int, denom: float,
               q_shared: bool = False, kv_shared: bool = False) -> torch.Tensor:
     """softmax((q . k) / denom) @ v for q [B (or 1), Nq, H*D], k / v [B (or 1), Nk, H*D] (2-d row views) -> [B*Nq, H*D]."""
+    dev = _home("q", q)
+    for name, t, n in (("q", q, (1 if q_shared else B) * Nq), ("k", k, (1 if kv_shared else B) * Nk), ("v", v, (1 if kv_shared else B) * Nk)):
+        _t(name, t, _F32, (None, H * D), dev, rows=True)
+        _need(n >= 1 and t.shape[0] >= n, f"{name} has {t.shape[0]} rows, the kernel reads {n}")
     out = torch.empty((B * Nq, H * D), dtype=torch.float32, device=q.device)
     _lib.check(_lib.load().msam_strict_attention(
         q.data_ptr(), q.stride(0), 0 if q_shared else Nq * q.stride(0), k.data_ptr(), k.stride(0), 0 if kv_shared else Nk * k.stride(0),
@@ -216,8 +249,23 @@ def i2t_block(keys: torch.Tensor, shared: bool, pos: torch.Tensor, wq, tok_k: to
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``norm4(keys + cross_attn_image_to_token(q=keys + pos, k, v))`` in one launch (``msam_strict_i2t_block``): keys [B*T, 256] rows
     (``shared``: [T, 256] for every prompt), tok_k / tok_v [B*Tk, 128] the token side's projections, wq / wo (weight, bias)."""
+    dev = _home("keys", keys)
+    _need(B >= 1 and Tk >= 1, f"B = {B} and Tk = {Tk} must be positive")
+    _t("keys", keys, _F32, (T if shared else B * T, PROMPT_DIM), dev)
+    _t("pos", pos, _F32, (T, PROMPT_DIM), dev)
+    _t("wq[0]", wq[0], _F32, (128, PROMPT_DIM), dev)
+    _t("wq[1]", wq[1], _F32, (128,), dev)
+    _t("wo[0]", wo[0], _F32, (PROMPT_DIM, 128), dev)
+    _t("wo[1]", wo[1], _F32, (PROMPT_DIM,), dev)
+    _t("tok_k", tok_k, _F32, (None, 128), dev, rows=True)
+    _t("tok_v", tok_v, _F32, tuple(tok_k.shape), dev, rows=True)
+    _need(tok_k.shape[0] >= B * Tk and tok_v.stride(0) == tok_k.stride(0),
+          f"tok_k / tok_v must hold B * Tk = {B * Tk} rows with one row stride, got {list(tok_k.shape)}")
+    _t("norm[0]", norm[0], _F32, (PROMPT_DIM,), dev)
+    _t("norm[1]", norm[1], _F32, (PROMPT_DIM,), dev)
     if out is None:
         out = torch.empty((B * T, PROMPT_DIM), dtype=torch.float32, device=pos.device) if shared else keys
+    _t("out", out, _F32, (B * T, PROMPT_DIM), dev)
     p = _lib.SI2TParams()
     p.keys, p.key_batch_stride, p.pos = keys.data_ptr(), (0 if shared else T * PROMPT_DIM), pos.data_ptr()
     p.wq, p.bq, p.wo, p.bo = wq[0].data_ptr(), wq[1].data_ptr(), wo[0].data_ptr(), wo[1].data_ptr()
