@@ -286,8 +286,8 @@ int msam_mask_nms(const uint32_t* bits, const int32_t* order, const float* boxes
  * threshold / crop-edge filters, greedy box NMS, paint by descending area, connected components, drop the largest component
  * (with_background) and components below min_object_size, consecutive relabel.  1 <= N <= 4096 candidates: iou / stability
  * fp32 [N], boxes int32 [N,4] xyxy in the crop frame, area int32 [N], bits uint32 [N, ceil(H/32), W]; crop_box: HOST int32[4]
- * (x0, y0, x1, y1); labels int32 [H, W]; flag int32 [1] reads 0 when the component labelling converged.  No host
- * synchronisation; 15 kernels on `stream`. */
+ * (x0, y0, x1, y1); labels int32 [H, W]; flag int32 [1] reads 0 when the component labelling is complete.  No host
+ * synchronisation; 13 kernels on `stream`. */
 int64_t msam_amg_generate_workspace_bytes(int32_t N, int32_t H, int32_t W);
 int msam_amg_generate_labels(const float* iou, const float* stability, const int32_t* boxes, const int32_t* area,
                              const uint32_t* bits, int32_t N, int32_t H, int32_t W, const int32_t* crop_box,
@@ -604,16 +604,19 @@ int msam_paint_label_image_dev(const uint32_t* bits, const int32_t* order, const
  * roots[i] = KEY of the root of pixel i's component, -1 for background.  A pixel's key is its position in block-major order
  * (512 x 512 blocks in raster order, raster order inside a block), the root is the component's smallest key; ascending root keys
  * reproduce the reference's component numbering (per-block labels with running offsets, union across faces, consecutive by first
- * occurrence).  For H, W <= 512 key == linear index.  changed_flag: int32 device scratch.
- * Synchronises the stream once per union pass (at most max_iters, default 8); iters_done (host, optional). */
+ * occurrence).  For H, W <= 512 key == linear index.  changed_flag: int32 device memory, 0 afterwards (see the async variant).
+ * Synchronises the stream once.  The labelling is complete after one run: max_iters is kept for the ABI and ignored,
+ * iters_done (host, optional) reports 1. */
 int msam_label_components(const int32_t* seg, int32_t H, int32_t W, int32_t* roots, int32_t* changed_flag,
                           int32_t max_iters, int32_t* iters_done, void* stream);
 
 /* sizes[r] = number of pixels whose root is r (int32 [n], zeroed here), bg_count[0] = number of background pixels
  * (roots[i] < 0): the `unique(..., return_counts=True)` of util.py:1837 keyed by root index. */
 int msam_component_sizes(const int32_t* roots, int32_t n, int32_t* sizes, int32_t* bg_count, void* stream);
-/* Fully asynchronous variant: `passes` union passes (one is complete for the lock-free union, a second one verifies),
- * changed_flag = flag of the last pass to be checked by the caller whenever convenient. */
+/* Fully asynchronous variant (3 kernels: tiles labelled in LDS, unions across the tile borders, one compression).  `passes`
+ * (>= 1) is kept for the ABI: the labelling runs once whatever it says.  changed_flag: 0 = complete; non-zero = the compression
+ * pass met an equal-valued 4-edge whose ends have different roots (never expected; to be checked by the caller whenever
+ * convenient). */
 int msam_label_components_async(const int32_t* seg, int32_t H, int32_t W, int32_t* roots, int32_t* changed_flag,
                                 int32_t passes, void* stream);
 

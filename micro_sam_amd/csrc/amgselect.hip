@@ -1,14 +1,15 @@
 // AutomaticMaskGenerator.generate(output_mode="instance_segmentation") for the single-crop device state, as ONE call that
-// enqueues 15 kernels and no torch operator (reference: AMGBase._postprocess_batch micro_sam/instance_segmentation.py:99-144 -
+// enqueues 13 kernels and no torch operator (reference: AMGBase._postprocess_batch micro_sam/instance_segmentation.py:99-144 -
 // predicted-IoU / stability / crop-edge filters + box NMS - and util.mask_data_to_segmentation util.py:1773-1848 - paint by
 // descending area, connected components, drop the largest component (with_background) and the small ones, relabel
 // consecutively).  Integer / compare work on <= 4096 candidates and one label image: latency-bound, no GEMM shape.
 //
 //   amg_select_sort_kernel   filters -> valid flags; stable descending sort of the scores (bitonic sort of 64-bit
-//                            (inverted ordered score, index) keys in LDS, one workgroup) -> order, sorted boxes / flags
-//   nms_mask / nms_sweep64   (segment.hip) greedy NMS on the sorted boxes
-//   amg_area_sort_kernel     kept flags back to candidate order, stable descending sort by area -> paint order + count
-//   paint / cc_*             (segment.hip) label image from the bit masks, union-find components, component sizes
+//                            (inverted ordered score, index) keys in LDS, one workgroup) -> order, sorted boxes / flags and
+//                            V = the number of leading sorted positions that can hold a valid candidate (device memory)
+//   nms_mask / nms_sweep64   (segment.hip) greedy NMS on the first V sorted boxes
+//   amg_area_sort_kernel     stable descending sort by area of the kept ones among the first V -> paint order + count
+//   paint / cc_*             (segment.hip) label image from the bit masks, components (tile, border, compress + check), sizes
 //   relabel_*                per-block root statistics -> one-workgroup scan (+ largest-component decision) -> new ids at the
 //                            roots -> gather
 #include "common.h"
@@ -16,8 +17,8 @@
 
 void msam_set_error(const char* msg);
 int msam_check_launch(const char* what);
-extern "C" int msam_box_nms_valid(const float* boxes_sorted, const int32_t* valid_sorted, int32_t K, float iou_threshold,
-                                  uint64_t* mask_scratch, int32_t* keep_flags, void* stream);
+int msam_box_nms_valid_dev(const float* boxes_sorted, const int32_t* valid_sorted, const int32_t* v_dev, int32_t K, float iou_threshold,
+                           uint64_t* mask_scratch, int32_t* keep_flags, void* stream);
 extern "C" int msam_paint_label_image_dev(const uint32_t* bits, const int32_t* order, const int32_t* k_dev, int32_t H, int32_t W,
                                           int32_t* label, void* stream);
 extern "C" int msam_label_components_async(const int32_t* seg, int32_t H, int32_t W, int32_t* roots, int32_t* changed_flag,
@@ -34,13 +35,15 @@ MSAM_DEVINL uint32_t f2ord(float f) {            // order-preserving float -> ui
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
-// ascending bitonic sort of 4096 64-bit keys in LDS by 1024 threads
-MSAM_DEVINL void bitonic4096(u64* keys, int tid) {
-    for (int k = 2; k <= NMAX; k <<= 1) {
+MSAM_DEVINL int pow2_ceil(int n) { return n <= 1 ? 1 : 1 << (32 - __clz(n - 1)); }
+
+// ascending bitonic sort of the first n2 (a power of two <= 4096, the same for the whole workgroup) 64-bit keys in LDS by 1024
+// threads.  Keys are distinct (the candidate index is part of them), so the order of the live keys does not depend on n2 as long
+// as the padding keys ~0 sort behind them.
+MSAM_DEVINL void bitonic_lds(u64* keys, int n2, int tid) {
+    for (int k = 2; k <= n2; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
-#pragma unroll
-            for (int rep = 0; rep < 2; ++rep) {
-                const int t = tid + rep * NT;
+            for (int t = tid; t < (n2 >> 1); t += NT) {
                 const int i = ((t / j) * 2 * j) + (t % j), p = i + j;
                 const bool asc = (i & k) == 0;
                 const u64 a = keys[i], b = keys[p];
@@ -54,15 +57,17 @@ MSAM_DEVINL void bitonic4096(u64* keys, int tid) {
 struct SelArgs {
     const float* iou; const float* stab; const int* boxes; int N;
     float iou_thr, stab_thr; int x0, y0, x1, y1, W, H;
-    int* order; float* boxes_sorted; int* valid_sorted;
+    int* order; float* boxes_sorted; int* valid_sorted; int* v_dev;
 };
 
 __global__ __launch_bounds__(NT) void amg_select_sort_kernel(SelArgs a) {
     __shared__ u64 keys[NMAX];
-    const int tid = threadIdx.x;
+    __shared__ int vend;
+    const int tid = threadIdx.x, n2 = pow2_ceil(a.N);
     const float crop[4] = {(float)a.x0, (float)a.y0, (float)a.x1, (float)a.y1};
     const float orig[4] = {0.f, 0.f, (float)a.W, (float)a.H};
-    for (int i = tid; i < NMAX; i += NT) {
+    if (tid == 0) vend = 0;
+    for (int i = tid; i < n2; i += NT) {
         u64 key = ~0ull;
         if (i < a.N) {
             bool valid = true;
@@ -83,38 +88,51 @@ __global__ __launch_bounds__(NT) void amg_select_sort_kernel(SelArgs a) {
         keys[i] = key;
     }
     __syncthreads();
-    bitonic4096(keys, tid);
+    bitonic_lds(keys, n2, tid);
+    int last = 0;                                        // 1 + the last sorted position of a valid candidate that this thread saw
     for (int i = tid; i < a.N; i += NT) {
         const uint32_t lo = (uint32_t)keys[i];
         const int idx = (int)(lo & 0x7fffffffu);
         a.order[i] = idx;
         a.valid_sorted[i] = (int)(lo >> 31);
+        if (lo >> 31) last = i + 1;
 #pragma unroll
         for (int c = 0; c < 4; ++c) a.boxes_sorted[i * 4 + c] = (float)a.boxes[idx * 4 + c];
     }
+    // V: every position at or behind it holds a rejected candidate (their score key is -inf, so V is the number of valid ones
+    // unless a valid score is -inf or NaN itself - taking the last valid position covers that too)
+    if (last) atomicMax(&vend, last);
+    __syncthreads();
+    if (tid == 0) *a.v_dev = vend;
 }
 
-// keep flags (sorted order) -> candidate order; stable area-descending order of the selected masks + their count
+// stable area-descending order of the selected masks + their count.  Only the first V = *v_dev sorted positions can hold a kept
+// candidate (amg_select_sort_kernel), so V keys are sorted; order2 is written for its first min(N, pow2_ceil(V)) entries, of which
+// paint reads the first *k_dev.
 __global__ __launch_bounds__(NT) void amg_area_sort_kernel(const int* __restrict__ order, const int* __restrict__ keep_sorted,
                                                            const int* __restrict__ area, int N, int min_size,
-                                                           int* __restrict__ order2, int* __restrict__ k_dev) {
+                                                           const int* __restrict__ v_dev, int* __restrict__ order2,
+                                                           int* __restrict__ k_dev) {
     __shared__ u64 keys[NMAX];
     __shared__ int count;
-    const int tid = threadIdx.x;
+    const int tid = threadIdx.x, V = min(max(*v_dev, 0), N), n2 = pow2_ceil(V);
     if (tid == 0) count = 0;
-    for (int i = tid; i < NMAX; i += NT) keys[i] = ~0ull;
     __syncthreads();
-    for (int i = tid; i < N; i += NT) {
-        const int idx = order[i];
-        const int ar = area[idx];
-        const bool sel = keep_sorted[i] != 0 && (min_size <= 0 || ar >= min_size);
-        // descending area, ties by ascending candidate index; unselected masks sink to the end
-        keys[idx] = sel ? (((u64)(uint32_t)(0x7fffffff - ar) << 32) | (u64)(uint32_t)idx) : ((0xfffffffeull << 32) | (u64)(uint32_t)idx);
-        if (sel) atomicAdd(&count, 1);
+    for (int i = tid; i < n2; i += NT) {
+        u64 key = ~0ull;
+        if (i < V) {
+            const int idx = order[i];
+            const int ar = area[idx];
+            const bool sel = keep_sorted[i] != 0 && (min_size <= 0 || ar >= min_size);
+            // descending area, ties by ascending candidate index; unselected masks sink to the end
+            key = sel ? (((u64)(uint32_t)(0x7fffffff - ar) << 32) | (u64)(uint32_t)idx) : ((0xfffffffeull << 32) | (u64)(uint32_t)idx);
+            if (sel) atomicAdd(&count, 1);
+        }
+        keys[i] = key;
     }
     __syncthreads();
-    bitonic4096(keys, tid);
-    for (int i = tid; i < N; i += NT) order2[i] = (int)(uint32_t)keys[i];
+    bitonic_lds(keys, n2, tid);
+    for (int i = tid; i < min(N, n2); i += NT) order2[i] = (int)(uint32_t)keys[i];
     if (tid == 0) *k_dev = count;
 }
 
@@ -265,20 +283,20 @@ extern "C" int msam_amg_generate_labels(const float* iou, const float* stability
     int* order2 = (int*)take(4LL * N);
     float* boxes_sorted = (float*)take(16LL * N);
     uint64_t* scratch = (uint64_t*)take(8LL * N * nblk);
-    int* small = (int*)take(256);                    // [0] k_dev, [1] bg count, [2] drop index
+    int* small = (int*)take(256);                    // [0] k_dev, [1] bg count, [2] drop index, [3] V (amg_select_sort_kernel)
     int* painted = (int*)take(4LL * n); int* roots = (int*)take(4LL * n); int* sizes = (int*)take(4LL * n); int* newid = (int*)take(4LL * n);
     int* blk_cnt = (int*)take(4LL * nb); int* blk_off = (int*)take(4LL * nb);
     u64* blk_max = (u64*)take(8LL * nb);
     int e;
     SelArgs a{iou, stability, boxes, N, pred_iou_thresh, stability_score_thresh, crop_box[0], crop_box[1], crop_box[2], crop_box[3],
-              W, H, order, boxes_sorted, valid_sorted};
+              W, H, order, boxes_sorted, valid_sorted, small + 3};
     hipLaunchKernelGGL(amg_select_sort_kernel, dim3(1), dim3(NT), 0, s, a);
     if ((e = msam_check_launch("amg_select_sort"))) return e;
-    if ((e = msam_box_nms_valid(boxes_sorted, valid_sorted, N, box_nms_thresh, scratch, keep_sorted, s))) return e;
-    hipLaunchKernelGGL(amg_area_sort_kernel, dim3(1), dim3(NT), 0, s, order, keep_sorted, area, N, min_object_size, order2, small);
+    if ((e = msam_box_nms_valid_dev(boxes_sorted, valid_sorted, small + 3, N, box_nms_thresh, scratch, keep_sorted, s))) return e;
+    hipLaunchKernelGGL(amg_area_sort_kernel, dim3(1), dim3(NT), 0, s, order, keep_sorted, area, N, min_object_size, small + 3, order2, small);
     if ((e = msam_check_launch("amg_area_sort"))) return e;
     if ((e = msam_paint_label_image_dev(bits, order2, small, H, W, painted, s))) return e;
-    if ((e = msam_label_components_async(painted, H, W, roots, flag, 2, s))) return e;
+    if ((e = msam_label_components_async(painted, H, W, roots, flag, 1, s))) return e;
     if ((e = msam_component_sizes(roots, n, sizes, small + 1, s))) return e;
     hipLaunchKernelGGL(relabel_stats_kernel, dim3(nb), dim3(256), 0, s, roots, sizes, n, H, W, min_object_size, blk_cnt, blk_max);
     hipLaunchKernelGGL(relabel_scan_kernel, dim3(1), dim3(NT), 0, s, blk_cnt, blk_max, nb, small + 1, with_background,
@@ -291,7 +309,7 @@ extern "C" int msam_amg_generate_labels(const float* iou, const float* stability
 // util.mask_data_to_segmentation(label_masks=True, merge_exclusively=False) for K masks that are already selected (reference
 // micro_sam/util.py:1773-1848): paint in the given order (later masks overwrite), connected components, drop components below
 // min_object_size and - with_background - the largest one counting label 0, consecutive relabel: the tail of
-// msam_amg_generate_labels as its own entry point (7 kernels, no host synchronisation).  bits uint32 [*, ceil(H/32), W]; order int32 [K]
+// msam_amg_generate_labels as its own entry point (9 kernels, no host synchronisation).  bits uint32 [*, ceil(H/32), W]; order int32 [K]
 // = mask indices in paint order (the caller sorts by area, stable, descending); K may also come from device memory (k_dev != NULL).
 extern "C" int64_t msam_labels_from_masks_workspace_bytes(int32_t H, int32_t W) {
     if (H <= 0 || W <= 0) return 0;
@@ -318,7 +336,7 @@ extern "C" int msam_labels_from_masks(const uint32_t* bits, const int32_t* order
     int e;
     if (k_dev) { if ((e = msam_paint_label_image_dev(bits, order, k_dev, H, W, painted, s))) return e; }
     else if ((e = msam_paint_label_image(bits, order, K, H, W, painted, s))) return e;
-    if ((e = msam_label_components_async(painted, H, W, roots, flag, 2, s))) return e;
+    if ((e = msam_label_components_async(painted, H, W, roots, flag, 1, s))) return e;
     if ((e = msam_component_sizes(roots, n, sizes, small + 1, s))) return e;
     hipLaunchKernelGGL(relabel_stats_kernel, dim3(nb), dim3(256), 0, s, roots, sizes, n, H, W, min_object_size, blk_cnt, blk_max);
     hipLaunchKernelGGL(relabel_scan_kernel, dim3(1), dim3(NT), 0, s, blk_cnt, blk_max, nb, small + 1, with_background,

@@ -5,8 +5,9 @@
 //   paint : the reference paints masks in area-descending order, later (smaller) masks overwrite earlier ones, so
 //           label(y,x) = rank+1 of the LAST mask in paint order that covers the pixel.  One thread per (32-row word,
 //           column): walks the masks from last to first, assigns the still-unassigned bits, stops when all 32 are done.
-//   label : label-equivalence union-find over block-major KEYS (common.h bm_key): hook (smaller key becomes the root) +
-//           pointer-jumping compression, iterated until no hook fires.  The root key of a component is its first pixel in the
+//   label : union-find over block-major KEYS (common.h bm_key; the smaller key becomes the root) in two levels: every 64 x 32 tile
+//           is labelled in LDS (row runs + column unions), the edges that cross a tile border are united in global memory, one
+//           pass compresses every pixel to its root and checks every edge.  The root key of a component is its first pixel in the
 //           reference's labelling order (elf.parallel.label over 512 x 512 blocks), so ascending root keys == its numbering.
 //   overlap : contingency table between consecutive slices of a label volume (the nifty.ground_truth.overlap behind
 //           elf.tracking compute_edges_from_overlap, called by merge_instance_segmentation_3d,
@@ -47,44 +48,142 @@ __global__ __launch_bounds__(256) void paint_kernel(const uint32_t* __restrict__
 // L[p] (pixel-indexed) holds the KEY (common.h bm_key: block-major order = the reference's component numbering) of the parent of
 // pixel p's tree node, -1 for background; the node of key q lives at pixel bm_pix(q).  Keys order the unions (smaller key = root),
 // so a converged root key is the component's first pixel in block-major order.
-__global__ __launch_bounds__(256) void cc_init_kernel(const int* __restrict__ seg, int H, int W, int* __restrict__ L) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < H * W) L[i] = seg[i] != 0 ? bm_key(i, H, W) : -1;
-}
-
 __device__ __forceinline__ int cc_find(const int* L, int i, int H, int W) {       // root KEY of the tree that pixel i is in
     int r = L[i];
     while (true) { const int p = L[bm_pix(r, H, W)]; if (p == r) break; r = p; }
     return r;
 }
 
-// hook: for every foreground pixel join with the right and the lower neighbour of equal value (covers every 4-edge once)
-__global__ __launch_bounds__(256) void cc_hook_kernel(const int* __restrict__ seg, int H, int W, int* L, int* __restrict__ changed) {
+// ---- level 1: one workgroup labels a CC_TW x CC_TH tile in LDS on tile-local raster indices and writes, per pixel, the block-major
+// key of its tile-local root.  CC_TW and CC_TH divide 512, so a tile lies inside one 512 x 512 block of bm_key, where the key grows
+// with the raster index: the smallest local index of a component is its smallest key in the tile.  A wave owns 8 rows (lane = column):
+//   1. row runs     par[p] = first pixel of p's horizontal run of equal value (a ballot and a bit scan, no atomics)
+//   2. column edges lock-free union (smaller index wins) of the runs above and below an equal-valued vertical edge; an edge whose left
+//                   neighbour edge joins the same two runs is skipped
+//   3. every pixel walks to its root and writes the root's key
+constexpr int CC_TW = 64, CC_TH = 32, CC_ROWS = CC_TH / 4;
+static_assert(CC_TW == 64 && 512 % CC_TW == 0 && 512 % CC_TH == 0, "a tile is one wave wide and nests inside the 512 x 512 blocks");
+
+__device__ __forceinline__ int cc_find_lds(const int* par, int i) {
+    int r = par[i];
+    while (true) { const int p = par[r]; if (p == r) break; r = p; }
+    return r;
+}
+
+__global__ __launch_bounds__(256) void cc_tile_kernel(const int* __restrict__ seg, int H, int W, int* __restrict__ L) {
+    __shared__ int par[CC_TW * CC_TH];
+    const int lane = threadIdx.x & 63, r0 = (threadIdx.x >> 6) * CC_ROWS;
+    const int tx0 = blockIdx.x * CC_TW, ty0 = blockIdx.y * CC_TH;
+    const int gx = tx0 + lane;
+    int v[CC_ROWS + 1];                                   // this lane's column: the wave's rows and the row below them
+#pragma unroll
+    for (int k = 0; k <= CC_ROWS; ++k) {
+        const int gy = ty0 + r0 + k;
+        v[k] = (gx < W && gy < H && r0 + k < CC_TH) ? seg[(long)gy * W + gx] : 0;
+    }
+    unsigned long long vert = 0ull;                        // bit k: the edge below row k needs a union
+#pragma unroll
+    for (int k = 0; k < CC_ROWS; ++k) {
+        const int left = __shfl_up(v[k], 1), dleft = __shfl_up(v[k + 1], 1);
+        const bool cont = lane > 0 && left == v[k];       // continues the run of the pixel to the left
+        const unsigned long long starts = __ballot(v[k] != 0 && !cont);
+        const unsigned long long upto = starts & ((2ull << lane) - 1ull);                   // (lane 63: 2 << 63 wraps to 0, mask = all ones)
+        const uint32_t hi = (uint32_t)(upto >> 32);
+        const int start = hi ? 63 - __clz(hi) : 31 - __clz((uint32_t)upto);                 // last run start at or before this lane
+        par[(r0 + k) * CC_TW + lane] = v[k] != 0 ? (r0 + k) * CC_TW + start : -1;
+        if (v[k] != 0 && v[k + 1] == v[k] && !(cont && dleft == v[k])) vert |= 1ull << k;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < CC_ROWS; ++k) {
+        if (!((vert >> k) & 1ull)) continue;
+        int a = cc_find_lds(par, (r0 + k) * CC_TW + lane), b = cc_find_lds(par, (r0 + k + 1) * CC_TW + lane);
+        while (a != b) {                                   // as in cc_border_kernel, on LDS
+            if (a < b) { const int t = a; a = b; b = t; }
+            const int old = atomicMin(&par[a], b);
+            if (old == a) break;
+            a = old;
+        }
+    }
+    __syncthreads();
+    // key of the local pixel (ly, lx): base + ly * bw + lx
+    const int by = ty0 >> 9, bx = tx0 >> 9;
+    const int bh = min(512, H - (by << 9)), bw = min(512, W - (bx << 9));
+    const int base = (by << 9) * W + (bx << 9) * bh + (ty0 & 511) * bw + (tx0 & 511);
+#pragma unroll
+    for (int k = 0; k < CC_ROWS; ++k) {
+        const int gy = ty0 + r0 + k;
+        if (gx >= W || gy >= H) continue;
+        int key = -1;
+        if (v[k] != 0) {
+            const int r = cc_find_lds(par, (r0 + k) * CC_TW + lane);
+            key = base + (r / CC_TW) * bw + (r % CC_TW);
+        }
+        L[(long)gy * W + gx] = key;
+    }
+}
+
+// ---- level 2: one thread per pixel on the right or the lower border of a tile; an equal-valued edge across the border is united on
+// the global array (lock-free, the smaller key wins).  An edge is left out when the previous edge along the same border, inside the
+// same pair of tiles, has the same value on both sides: level 1 has joined the end points of the two edges on either side already.
+//
+// Why one pass is complete: the union loop leaves an edge (i, j) only when it saw the two roots equal or when its atomicMin hooked
+// the larger root a under b (old == a).  When another thread moved a first (old != a), L[a] = min(old, b) may have dropped the link
+// a -> old, and the loop goes on with (old, b) until that pair is joined as well, so no link is ever lost: parents only decrease,
+// trees only grow together, and when the kernel has ended the end points of every edge it visited lie in one tree.  Together with
+// level 1 (every edge inside a tile) that is every 4-edge of the image, so one compression gives the final roots, and the smallest
+// key of a tree is its root because a parent is never larger than its child.  cc_compress_check_kernel is the runtime witness.
+__global__ __launch_bounds__(256) void cc_border_kernel(const int* __restrict__ seg, int H, int W, int nvx, int* L) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int nv = nvx * H, nhy = (H - 1) / CC_TH;
+    int i, j, prev;                                        // prev: offset of the previous edge along the border, 0 = first of its tile pair
+    if (t < nv) {                                          // right border of tile column c: x = c * CC_TW + CC_TW - 1, x + 1 < W
+        const int c = t / H, y = t - c * H;
+        i = y * W + c * CC_TW + CC_TW - 1; j = i + 1;
+        prev = (y % CC_TH) != 0 ? W : 0;
+    } else {                                               // lower border of tile row r: y = r * CC_TH + CC_TH - 1, y + 1 < H
+        const int u = t - nv;
+        if (u >= nhy * W) return;
+        const int r = u / W, x = u - r * W;
+        i = (r * CC_TH + CC_TH - 1) * W + x; j = i + W;
+        prev = (x % CC_TW) != 0 ? 1 : 0;
+    }
+    const int v = seg[i];
+    if (v == 0 || seg[j] != v) return;
+    if (prev && seg[i - prev] == v && seg[j - prev] == v) return;
+    int a = cc_find(L, i, H, W), b = cc_find(L, j, H, W);
+    while (a != b) {                                       // union by smaller key (lock-free)
+        if (a < b) { const int tmp = a; a = b; b = tmp; }  // a > b
+        const int old = atomicMin(&L[bm_pix(a, H, W)], b);
+        if (old == a) break;
+        a = old;                                           // someone hooked a elsewhere: continue from there
+    }
+}
+
+// ---- compression + check: every pixel takes its root; `incomplete` is set when a foreground pixel and an equal-valued right or lower
+// neighbour end in different roots (cannot happen, see cc_border_kernel; callers raise on it).  A neighbour's entry is, at any time,
+// the key of one of its ancestors: if it equals this pixel's entry or root, the two share a tree and nothing is walked.
+__global__ __launch_bounds__(256) void cc_compress_check_kernel(const int* __restrict__ seg, int H, int W, int* L,
+                                                                int* __restrict__ incomplete) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= H * W) return;
     const int v = seg[i];
     if (v == 0) return;
+    const int raw = L[i];
+    int r = raw;
+    while (true) { const int p = L[bm_pix(r, H, W)]; if (p == r) break; r = p; }
+    if (r != raw) L[i] = r;
     const int y = i / W, x = i - y * W;
-    int any = 0;
+    bool bad = false;
 #pragma unroll
     for (int d = 0; d < 2; ++d) {
         const int j = d == 0 ? (x + 1 < W ? i + 1 : -1) : (y + 1 < H ? i + W : -1);
         if (j < 0 || seg[j] != v) continue;
-        int a = cc_find(L, i, H, W), b = cc_find(L, j, H, W);
-        while (a != b) {                       // union by smaller key (lock-free)
-            if (a < b) { const int t = a; a = b; b = t; }      // a > b
-            const int old = atomicMin(&L[bm_pix(a, H, W)], b);
-            if (old == a) { any = 1; break; }
-            a = old;                            // someone hooked a elsewhere: continue from there
-            any = 1;
-        }
+        const int q = L[j];
+        if (q == raw || q == r) continue;
+        bad = bad || cc_find(L, j, H, W) != r;
     }
-    if (any) *changed = 1;
-}
-
-__global__ __launch_bounds__(256) void cc_compress_kernel(int H, int W, int* L) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < H * W && L[i] >= 0) L[i] = cc_find(L, i, H, W);
+    if (bad) *incomplete = 1;
 }
 
 // Component sizes keyed by root KEY: sizes[root key] += 1 for every foreground pixel.  A plain scatter-add puts hundreds
@@ -126,11 +225,21 @@ __global__ __launch_bounds__(256) void cc_sizes_kernel(const int* __restrict__ r
     if (threadIdx.x == 0 && bg) atomicAdd(bg_count, bg);
 }
 
-// ---- greedy box NMS (torchvision.ops.nms semantics) on score-sorted boxes: suppression bit matrix + serial sweep
-__global__ __launch_bounds__(64) void nms_mask_kernel(const float* __restrict__ boxes, int K, float thr,
+// ---- greedy box NMS (torchvision.ops.nms semantics) on score-sorted boxes: suppression bit matrix + serial sweep.
+// v_dev (optional, device memory): every box at or behind position *v_dev is rejected by `valid` (generate(): the rejected candidates
+// sort behind the others).  Such a box neither survives nor suppresses, so with vb = ceil(*v_dev / 64) the matrix blocks of row or
+// column block >= vb are neither written nor read, the sweep ends after vb blocks and the keep flags behind them are 0.  The grids
+// and the row stride of the matrix stay sized by K: the host never learns *v_dev.
+__device__ __forceinline__ int nms_live_blocks(const int* v_dev, int K) {
+    const int nblk = (K + 63) >> 6;
+    return v_dev ? min(nblk, (max(*v_dev, 0) + 63) >> 6) : nblk;
+}
+
+__global__ __launch_bounds__(64) void nms_mask_kernel(const float* __restrict__ boxes, int K, float thr, const int* __restrict__ v_dev,
                                                       unsigned long long* __restrict__ mask) {
     const int rb = blockIdx.y, cb = blockIdx.x, t = threadIdx.x;
-    const int nblk = (K + 63) >> 6;
+    const int nblk = (K + 63) >> 6, vb = nms_live_blocks(v_dev, K);
+    if (rb >= vb || cb >= vb) return;
     __shared__ float cbx[64][4];
     const int cj = cb * 64 + t;
     if (cj < K) { cbx[t][0] = boxes[cj * 4]; cbx[t][1] = boxes[cj * 4 + 1]; cbx[t][2] = boxes[cj * 4 + 2]; cbx[t][3] = boxes[cj * 4 + 3]; }
@@ -156,21 +265,23 @@ __global__ __launch_bounds__(64) void nms_mask_kernel(const float* __restrict__ 
 
 // one wave: lane l owns words l, l+64, ... of the running "removed" set (K <= 64*64*4 words handled by the stride loop)
 __global__ __launch_bounds__(64) void nms_sweep_kernel(const unsigned long long* __restrict__ mask, int K,
-                                                       const int* __restrict__ valid, int* __restrict__ keep) {
-    const int nblk = (K + 63) >> 6, lane = threadIdx.x;
+                                                       const int* __restrict__ valid, const int* __restrict__ v_dev,
+                                                       int* __restrict__ keep) {
+    const int nblk = (K + 63) >> 6, lane = threadIdx.x, vb = nms_live_blocks(v_dev, K), kv = min(K, vb * 64);
     extern __shared__ unsigned long long remv[];
-    for (int w = lane; w < nblk; w += 64) {
+    for (int i = kv + lane; i < K; i += 64) keep[i] = 0;
+    for (int w = lane; w < vb; w += 64) {
         unsigned long long r = 0ull;
         if (valid)                                   // boxes filtered out beforehand start as "removed"
             for (int b = 0; b < 64 && w * 64 + b < K; ++b) r |= (unsigned long long)(valid[w * 64 + b] == 0) << b;
         remv[w] = r;
     }
     __syncthreads();
-    for (int i = 0; i < K; ++i) {
+    for (int i = 0; i < kv; ++i) {
         const bool removed = (remv[i >> 6] >> (i & 63)) & 1ull;          // uniform across the wave
         if (lane == 0) keep[i] = removed ? 0 : 1;
         if (!removed)
-            for (int w = lane; w < nblk; w += 64) remv[w] |= mask[(long)i * nblk + w];
+            for (int w = lane; w < vb; w += 64) remv[w] |= mask[(long)i * nblk + w];
         __syncthreads();
     }
 }
@@ -179,16 +290,18 @@ __global__ __launch_bounds__(64) void nms_sweep_kernel(const unsigned long long*
 // resolves the 64 boxes of a block redundantly in registers (no barrier for the keep word), and the rows of the block are
 // OR-ed into the running "removed" set by all 256 threads with unconditional loads issued before the resolve.
 __global__ __launch_bounds__(256) void nms_sweep64_kernel(const unsigned long long* __restrict__ mask, int K,
-                                                          const int* __restrict__ valid, int* __restrict__ keep) {
+                                                          const int* __restrict__ valid, const int* __restrict__ v_dev,
+                                                          int* __restrict__ keep) {
     typedef unsigned long long u64;
-    const int nblk = (K + 63) >> 6, tid = threadIdx.x, lane = tid & 63, grp = tid >> 6;
+    const int nblk = (K + 63) >> 6, tid = threadIdx.x, lane = tid & 63, grp = tid >> 6, vb = nms_live_blocks(v_dev, K);
+    for (int i = vb * 64 + tid; i < K; i += 256) keep[i] = 0;
     extern __shared__ u64 sm[];
     u64* remv = sm;                    // [64]
     u64* diag = sm + 64;               // [nblk * 64]
     u64* part = diag + nblk * 64;      // [4][64]
     if (tid < 64) {
         u64 r = 0ull;
-        if (tid < nblk) {
+        if (tid < vb) {
             for (int b = 0; b < 64; ++b) {
                 const int i = tid * 64 + b;
                 if (i >= K || (valid && valid[i] == 0)) r |= 1ull << b;     // filtered / padding boxes start as "removed"
@@ -196,14 +309,14 @@ __global__ __launch_bounds__(256) void nms_sweep64_kernel(const unsigned long lo
         }
         remv[tid] = r;
     }
-    for (int i = tid; i < nblk * 64; i += 256) diag[i] = i < K ? mask[(long)i * nblk + (i >> 6)] : 0ull;
+    for (int i = tid; i < vb * 64; i += 256) diag[i] = i < K ? mask[(long)i * nblk + (i >> 6)] : 0ull;
     __syncthreads();
-    for (int b = 0; b < nblk; ++b) {
+    for (int b = 0; b < vb; ++b) {
         u64 rows[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const int r = b * 64 + grp * 16 + j;
-            rows[j] = (lane < nblk && lane > b && r < K) ? mask[(long)r * nblk + lane] : 0ull;
+            rows[j] = (lane < vb && lane > b && r < K) ? mask[(long)r * nblk + lane] : 0ull;
         }
         u64 cur = remv[b];
         const u64 d = diag[b * 64 + lane];
@@ -333,6 +446,8 @@ __global__ __launch_bounds__(256) void overlap_compact_kernel(const u64* __restr
 
 }  // namespace
 
+int msam_box_nms_valid_dev(const float* boxes_sorted, const int32_t* valid_sorted, const int32_t* v_dev, int32_t K, float iou_threshold,
+                           uint64_t* mask_scratch, int32_t* keep_flags, void* stream);
 extern "C" int msam_box_nms_valid(const float* boxes_sorted, const int32_t* valid_sorted, int32_t K, float iou_threshold,
                                   uint64_t* mask_scratch, int32_t* keep_flags, void* stream);
 
@@ -343,19 +458,26 @@ extern "C" int msam_box_nms(const float* boxes_sorted, int32_t K, float iou_thre
 
 extern "C" int msam_box_nms_valid(const float* boxes_sorted, const int32_t* valid_sorted, int32_t K, float iou_threshold,
                                   uint64_t* mask_scratch, int32_t* keep_flags, void* stream) {
+    return msam_box_nms_valid_dev(boxes_sorted, valid_sorted, nullptr, K, iou_threshold, mask_scratch, keep_flags, stream);
+}
+
+// msam_box_nms_valid with the number of leading positions that can hold a valid box in device memory (v_dev, may be NULL = K):
+// library-internal (amgselect.hip), see nms_mask_kernel
+int msam_box_nms_valid_dev(const float* boxes_sorted, const int32_t* valid_sorted, const int32_t* v_dev, int32_t K, float iou_threshold,
+                           uint64_t* mask_scratch, int32_t* keep_flags, void* stream) {
     if (K < 0 || (K > 0 && (!boxes_sorted || !mask_scratch || !keep_flags))) { msam_set_error("msam_box_nms: bad arguments"); return 1; }
     if (K == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int nblk = (K + 63) / 64;
     if (nblk * 8 > 60000) { msam_set_error("msam_box_nms: too many boxes"); return 1; }
-    hipLaunchKernelGGL(nms_mask_kernel, dim3(nblk, nblk), dim3(64), 0, s, boxes_sorted, K, iou_threshold,
+    hipLaunchKernelGGL(nms_mask_kernel, dim3(nblk, nblk), dim3(64), 0, s, boxes_sorted, K, iou_threshold, v_dev,
                        (unsigned long long*)mask_scratch);
     if (nblk <= 64)
         hipLaunchKernelGGL(nms_sweep64_kernel, dim3(1), dim3(256), (64 + nblk * 64 + 256) * 8, s,
-                           (const unsigned long long*)mask_scratch, K, valid_sorted, keep_flags);
+                           (const unsigned long long*)mask_scratch, K, valid_sorted, v_dev, keep_flags);
     else
         hipLaunchKernelGGL(nms_sweep_kernel, dim3(1), dim3(64), nblk * 8, s, (const unsigned long long*)mask_scratch, K,
-                           valid_sorted, keep_flags);
+                           valid_sorted, v_dev, keep_flags);
     return msam_check_launch("msam_box_nms");
 }
 
@@ -389,41 +511,42 @@ extern "C" int msam_component_sizes(const int32_t* roots, int32_t n, int32_t* si
     return msam_check_launch("msam_component_sizes");
 }
 
-// Fixed number of union passes without host synchronisation; changed_flag holds the flag of the LAST pass (0 = converged).
+namespace {
+// tile labelling in LDS, border unions, one compression with the edge check: 3 kernels + the memset of the flag
+int cc_label_launch(const int32_t* seg, int32_t H, int32_t W, int32_t* roots, int32_t* flag, hipStream_t s) {
+    if (hipMemsetAsync(flag, 0, sizeof(int), s) != hipSuccess) return 2;
+    hipLaunchKernelGGL(cc_tile_kernel, dim3((W + CC_TW - 1) / CC_TW, (H + CC_TH - 1) / CC_TH), dim3(256), 0, s, seg, H, W, roots);
+    const int nvx = (W - 1) / CC_TW, nhy = (H - 1) / CC_TH;
+    const long edges = (long)nvx * H + (long)nhy * W;
+    if (edges > 0)
+        hipLaunchKernelGGL(cc_border_kernel, dim3((unsigned)((edges + 255) / 256)), dim3(256), 0, s, seg, H, W, nvx, roots);
+    hipLaunchKernelGGL(cc_compress_check_kernel, dim3((H * W + 255) / 256), dim3(256), 0, s, seg, H, W, roots, flag);
+    return 0;
+}
+}  // namespace
+
+// Without host synchronisation.  The labelling is complete after one run (cc_border_kernel); `passes` (>= 1) is kept for the ABI
+// and no longer repeats anything.  changed_flag: 0 = complete, non-zero = an equal-valued edge ended in two roots.
 extern "C" int msam_label_components_async(const int32_t* seg, int32_t H, int32_t W, int32_t* roots, int32_t* changed_flag,
                                            int32_t passes, void* stream) {
     if (!seg || !roots || !changed_flag || H <= 0 || W <= 0 || passes <= 0) { msam_set_error("msam_label_components_async: bad arguments"); return 1; }
-    hipStream_t s = (hipStream_t)stream;
-    const int n = H * W, grid = (n + 255) / 256;
-    hipLaunchKernelGGL(cc_init_kernel, dim3(grid), dim3(256), 0, s, seg, H, W, roots);
-    for (int it = 0; it < passes; ++it) {
-        if (hipMemsetAsync(changed_flag, 0, sizeof(int), s) != hipSuccess) { msam_set_error("msam_label_components_async: memset"); return 2; }
-        hipLaunchKernelGGL(cc_hook_kernel, dim3(grid), dim3(256), 0, s, seg, H, W, roots, changed_flag);
-        hipLaunchKernelGGL(cc_compress_kernel, dim3(grid), dim3(256), 0, s, H, W, roots);
-    }
+    if (cc_label_launch(seg, H, W, roots, changed_flag, (hipStream_t)stream)) { msam_set_error("msam_label_components_async: memset"); return 2; }
     return msam_check_launch("msam_label_components_async");
 }
 
+// Synchronous form: returns when the roots are written.  `max_iters` is kept for the ABI (the labelling runs once whatever it
+// says); iters_done reports 1.
 extern "C" int msam_label_components(const int32_t* seg, int32_t H, int32_t W, int32_t* roots, int32_t* changed_flag,
                                      int32_t max_iters, int32_t* iters_done, void* stream) {
+    (void)max_iters;
     if (!seg || !roots || !changed_flag || H <= 0 || W <= 0) { msam_set_error("msam_label_components: bad arguments"); return 1; }
     hipStream_t s = (hipStream_t)stream;
-    const int n = H * W, grid = (n + 255) / 256;
-    hipLaunchKernelGGL(cc_init_kernel, dim3(grid), dim3(256), 0, s, seg, H, W, roots);
-    int it = 0;
-    // the union loop inside cc_hook_kernel already merges whole trees, so one hook pass + compression is complete;
-    // further passes only confirm convergence (changed == 0) - bounded by max_iters
-    for (; it < (max_iters > 0 ? max_iters : 8); ++it) {
-        if (hipMemsetAsync(changed_flag, 0, sizeof(int), s) != hipSuccess) { msam_set_error("msam_label_components: memset"); return 2; }
-        hipLaunchKernelGGL(cc_hook_kernel, dim3(grid), dim3(256), 0, s, seg, H, W, roots, changed_flag);
-        hipLaunchKernelGGL(cc_compress_kernel, dim3(grid), dim3(256), 0, s, H, W, roots);
-        int h = 0;
-        if (hipMemcpyAsync(&h, changed_flag, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) { msam_set_error("msam_label_components: readback"); return 2; }
-        if (!h) { ++it; break; }
-    }
-    if (iters_done) *iters_done = it;
-    return msam_check_launch("msam_label_components");
+    if (cc_label_launch(seg, H, W, roots, changed_flag, s)) { msam_set_error("msam_label_components: memset"); return 2; }
+    const int e = msam_check_launch("msam_label_components");
+    if (e) return e;
+    if (hipStreamSynchronize(s) != hipSuccess) { msam_set_error("msam_label_components: synchronise"); return 2; }
+    if (iters_done) *iters_done = 1;
+    return 0;
 }
 
 // Greedy mask NMS: bits uint32 [K, ceil(H/32), W], order int32 [K] (descending score), boxes fp32 [K,4] xyxy and area int32 [K]
@@ -444,10 +567,10 @@ extern "C" int msam_mask_nms(const uint32_t* bits, const int32_t* order, const f
                        intersection_over_min, (unsigned long long*)mask_scratch);
     if (nblk <= 64)
         hipLaunchKernelGGL(nms_sweep64_kernel, dim3(1), dim3(256), (64 + nblk * 64 + 256) * 8, s,
-                           (const unsigned long long*)mask_scratch, K, (const int*)nullptr, keep_flags);
+                           (const unsigned long long*)mask_scratch, K, (const int*)nullptr, (const int*)nullptr, keep_flags);
     else
         hipLaunchKernelGGL(nms_sweep_kernel, dim3(1), dim3(64), nblk * 8, s, (const unsigned long long*)mask_scratch, K,
-                           (const int*)nullptr, keep_flags);
+                           (const int*)nullptr, (const int*)nullptr, keep_flags);
     return msam_check_launch("msam_mask_nms");
 }
 

@@ -494,7 +494,7 @@ class AutomaticMaskGenerator(AMGBase):
         data, crop_box = self.crop_list[0], self.crop_boxes[0]
         orig_h, orig_w = self.original_size
         if 0 < len(data) <= 4096 and tuple(crop_box) == (0, 0, orig_w, orig_h) and not getattr(self, "_torch_glue_generate", False):
-            # the whole chain as 15 kernels of one library call (csrc/amgselect.hip); the torch-operator formulation below
+            # the whole chain as 13 kernels of one library call (csrc/amgselect.hip); the torch-operator formulation below
             # is kept for states with more than 4096 candidates and as the cross-check of tests/test_gpu_segment.py
             return ops.amg_generate_labels(data["iou_preds"], data["stability_score"], data["boxes"], data["area"], data["bits"],
                                            self.original_size, crop_box, pred_iou_thresh, stability_score_thresh, box_nms_thresh,
@@ -521,12 +521,12 @@ class AutomaticMaskGenerator(AMGBase):
                 and tuple(self.crop_boxes[0]) == (0, 0, self.original_size[1], self.original_size[0])
                 and not getattr(self, "_general_generate", False)):
             # the default call on a single-crop device state: the whole of _postprocess_batch + mask_data_to_segmentation as ONE
-            # library call (generate_device: 15 kernels, no host synchronisation) and one download of label image + flag
+            # library call (generate_device: 13 kernels, no host synchronisation) and one download of label image + flag
             labels, flag = self.generate_device(pred_iou_thresh, stability_score_thresh, box_nms_thresh, with_background)
             out = util.fetch_to_host(torch.cat([labels.reshape(-1), flag]), tag="labels")
             if out[-1] == 0:
                 return out[:-1].reshape(self.original_size).view(np.uint32)
-            # (two union passes did not converge: the general path below iterates until they do)
+            # (the labelling reported an open edge: the general path below repeats it under host control)
         data = DeviceMaskData()
         on_device = len(self.crop_list) > 1 and all(
             isinstance(d, DeviceMaskData) and len(d) > 0 and all(torch.is_tensor(d[k]) and d[k].is_cuda for k in ("boxes", "iou_preds", "stability_score"))

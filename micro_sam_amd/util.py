@@ -1093,7 +1093,7 @@ def mask_data_to_segmentation_device(bits: torch.Tensor, areas: torch.Tensor, sh
     labels, flag = ops.labels_from_masks(bits, order, (h, w), k_dev=k_dev, min_object_size=min_object_size,
                                          with_background=with_background)
     out = fetch_to_host(torch.cat([labels.reshape(-1), flag]), tag="labels")    # one download: the label image + the convergence flag
-    if out[-1] != 0:                                                       # two union passes did not converge: iterate on the host's clock
+    if out[-1] != 0:                                                       # the labelling reported an open edge: repeat it on the host's clock
         return _mask_data_to_segmentation_device_iterative(bits, areas, shape, min_object_size, with_background)
     return out[:-1].reshape(h, w).view(np.uint32)
 

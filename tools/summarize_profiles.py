@@ -1,6 +1,7 @@
 """Turn the rocprofv3 outputs of a measurement run (gpurun_out/final_*) into the committed summaries under profiles/.
 
 Usage: python tools/summarize_profiles.py [round_tag]          (default r01)
+       python tools/summarize_profiles.py r08 --generate     (the generate() chain of a change next to its parent commit, see generate_chain)
 Inputs (files of the output folder GO below, written by tools/final_measure.sh, the commands quoted in profiles/<tag>_bench_kernel_summary.md):
   final_bench.log                    python bench.py --full                   (bench line incl. cpu_baseline)
   final_prof/*/*_kernel_stats.csv    rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline
@@ -46,7 +47,77 @@ def one(pattern):
     return max(files, key=os.path.getmtime)
 
 
+GEN_KERNELS = ("amg_select_sort", "nms_mask", "nms_sweep", "amg_area_sort", "paint_kernel", "cc_", "relabel_")
+
+
+def generate_chain():
+    """profiles/<tag>_generate_kernels.md: the kernels that msam_amg_generate_labels launches, parent commit next to the working tree.
+    Inputs in the folder gen of the output folder GO, all of one visit to one box: prof_parent / prof_change (rocprofv3 --kernel-trace --stats -- python
+    bench.py --no-cpu-baseline --no-side --lanes 1, the parent's from a checkout of HEAD built next to the tree), throughput.jsonl
+    (bench.py --steps 20 --warmup 5 with --lanes 3 and --lanes 1, parent and change alternating, one JSON record per run) and
+    dump_compare.json (bench.py --dump-outputs of both, array by array).  final_csrc_sha.txt names the measured change."""
+    sys.path.insert(0, ROOT)
+    import bench
+    gen = os.path.join(GO, "gen")
+    measured = open(os.path.join(GO, "final_csrc_sha.txt")).read().strip()
+    if measured != bench.csrc_sha16() and "--force" not in sys.argv:
+        raise SystemExit(f"{gen} was measured on csrc_sha16 {measured}, the working tree is {bench.csrc_sha16()}")
+    table, tiles, total = {}, {}, {}
+    for who in ("parent", "change"):
+        rows = list(csv.DictReader(open(one(os.path.join(gen, f"prof_{who}", "*", "*_kernel_stats.csv")))))
+        tiles[who] = next(int(r["Calls"]) for r in rows if "up_fused_kernel" in r["Name"])
+        total[who] = sum(float(r["TotalDurationNs"]) for r in rows) / 1e3 / tiles[who]
+        for r in rows:
+            name = r["Name"].replace("(anonymous namespace)::", "").split("(")[0].split("<")[0]
+            if any(k in name for k in GEN_KERNELS):
+                table.setdefault(name, {})[who] = (int(r["Calls"]), float(r["TotalDurationNs"]) / 1e3 / tiles[who])
+    os.makedirs(OUT, exist_ok=True)
+    with open(os.path.join(OUT, f"{TAG}_generate_kernels.md"), "w") as f:
+        f.write(f"# {TAG}: the kernels of `msam_amg_generate_labels`, parent commit and this change on one MI355X in one visit\n\n")
+        f.write(f"csrc_sha16 of the measured code: `{measured}`\n\n")
+        f.write("Command, once per build: `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --no-cpu-baseline --no-side "
+                "--lanes 1`.  us / tile = total kernel time over the launches of the once-per-tile `up_fused_kernel` "
+                f"({tiles['parent']} and {tiles['change']} tiles).  Memsets (4 per tile in the parent, 3 in the change) are not kernels "
+                "and are not listed.\n\n")
+        f.write("| kernel | parent launches / tile | parent us / tile | change launches / tile | change us / tile |\n|---|---|---|---|---|\n")
+        sums = {"parent": 0.0, "change": 0.0}
+        for name, d in sorted(table.items(), key=lambda kv: -max(v[1] for v in kv[1].values())):
+            cells = []
+            for who in ("parent", "change"):
+                if who in d:
+                    sums[who] += d[who][1]
+                    cells += [f"{d[who][0] / tiles[who]:.0f}", f"{d[who][1]:.1f}"]
+                else:
+                    cells += ["-", "-"]
+            f.write(f"| `{name}` | " + " | ".join(cells) + " |\n")
+        f.write(f"| **chain** | | **{sums['parent']:.1f}** | | **{sums['change']:.1f}** |\n")
+        f.write(f"| all kernels of the tile path | | {total['parent']:.0f} | | {total['change']:.0f} |\n\n")
+        f.write(f"Chain: {sums['change'] / sums['parent']:.2f} of the parent's time.\n\n")
+        tp = os.path.join(gen, "throughput.jsonl")
+        if os.path.exists(tp):
+            recs = [json.loads(l) for l in open(tp) if l.startswith("{")]
+            f.write("## Throughput\n\n`python bench.py --steps 20 --warmup 5 --lanes L`, parent and change alternating in one job, tiles/s in run order:\n\n")
+            f.write("| lanes | parent | change | slowest change > fastest parent |\n|---|---|---|---|\n")
+            for lanes in (3, 1):
+                v = {w: [r["value"] for r in recs if r["lanes"] == lanes and r["who"] == w] for w in ("parent", "change")}
+                if v["parent"] and v["change"]:
+                    f.write(f"| {lanes} | {', '.join(f'{x:.1f}' for x in v['parent'])} | {', '.join(f'{x:.1f}' for x in v['change'])} | "
+                            f"{'yes' if min(v['change']) > max(v['parent']) else 'no'} |\n")
+            f.write("\n")
+        dc = os.path.join(gen, "dump_compare.json")
+        if os.path.exists(dc):
+            d = json.load(open(dc))
+            f.write("## Output identity\n\n`bench.py --steps 3 --warmup 1 --dump-outputs DIR` of both builds, element for element: "
+                    + ", ".join(f"`{k}` {v['shape']} {'equal' if v['equal'] else str(v['differing']) + ' differ'}" for k, v in d.items()) + ".\n")
+        notes = os.path.join(OUT, f"{TAG}_generate_notes.md")           # hand-written reading of the table, kept next to it
+        if os.path.exists(notes):
+            f.write("\n" + open(notes).read())
+    print("wrote", os.path.join(OUT, f"{TAG}_generate_kernels.md"))
+
+
 def main():
+    if "--generate" in sys.argv:
+        return generate_chain()
     os.makedirs(OUT, exist_ok=True)
     # every table names the code it was measured on, and a measurement of OTHER code is refused (VERDICT r4 item 9: round 4's kernel
     # summary and SQ table described the build before the last csrc commit)
