@@ -42,23 +42,30 @@ def host_sam(tmp_path_factory):
         os.environ.pop("MSAM_EMU_CUS", None)
 
 
-@pytest.mark.parametrize("chain", [0, 1])
+@pytest.mark.parametrize("chain", [0, 1, pytest.param(2, id="chained-9-prompts-8-tokens-single-mask")])
 def test_decode_on_the_host_library_matches_the_oracle(host_sam, chain):
+    """chain 2: the chained route on a ragged launch (9 prompts: two 4-prompt groups and one over) of two points each (8 tokens per prompt,
+    labels 1 / 0 / -1) with the single-mask output - the smallest relative of tests/test_gpu_decoder_routes.py that runs without a GPU."""
     from oracle import sam_ref as S
     host, sam, sd = host_sam
     g = torch.Generator().manual_seed(4)
     feats = torch.randn(1, 256, 64, 64, generator=g) * 0.6
-    P = 8 if chain else 2          # (the chained form keeps its tables in the workspace of the stage-by-stage form: P >= 8 prompts)
-    pts = torch.rand(P, 1, 2, generator=g) * 1024
+    P = (9 if chain == 2 else 8) if chain else 2          # (the chained form keeps its tables in the workspace of the stage-by-stage form: P >= 8 prompts)
+    multimask = chain != 2
+    pts = torch.rand(P, 2 if chain == 2 else 1, 2, generator=g) * 1024
     lbl = torch.ones(P, 1, dtype=torch.int)
+    if chain == 2:
+        lbl = torch.tensor([[1, 1], [1, 0], [0, 1], [1, -1], [0, -1], [0, 0], [1, 1], [1, 0], [0, 1]], dtype=torch.int)
     with torch.no_grad():
-        _, iou_b, low_b = S.predict_torch(sd, feats, (1024, 1024), (1024, 1024), pts, lbl, return_logits=True, precision="bf16")
+        _, iou_b, low_b = S.predict_torch(sd, feats, (1024, 1024), (1024, 1024), pts, lbl, multimask_output=multimask, return_logits=True,
+                                          precision="bf16")
     assert host.msam_tune_set(b"dec_chain_min_p", 1 if chain else 128) == 0
     try:
         sam.invalidate()
-        low, iou = sam.decode(feats, pts, lbl)
+        low, iou = sam.decode(feats, pts, lbl, multimask_output=multimask)
     finally:
         host.msam_tune_set(b"dec_chain_min_p", 128)
+    assert low.shape == low_b.shape == (P, 3 if multimask else 1, 256, 256)
     scale = low_b.abs().max().item()
     d = (low - low_b).abs()
     assert torch.isfinite(low).all() and d.max().item() <= 0.03 * scale and d.mean().item() <= 0.006 * scale, (d.max().item() / scale, d.mean().item() / scale)
