@@ -621,6 +621,33 @@ int msam_label_components_async(const int32_t* seg, int32_t H, int32_t W, int32_
                                 int32_t passes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Label matching:  the contingency table, object counts and IoU edges behind elf.evaluation.matching /
+ * mean_segmentation_accuracy (micro_sam/evaluation/evaluation.py:44-45, instance_segmentation.py:184-185), for B
+ * predictions in one call (csrc/matching.hip)
+ * ------------------------------------------------------------------------------------------------- */
+#define MSAM_MATCH_MAX_THRESHOLDS 16
+#define MSAM_MATCH_MAX_BATCH 65535
+#define MSAM_MATCH_HEADER 4   /* result[0] = edges found (may exceed max_edges), result[1] = 1: edge list too small */
+#define MSAM_MATCH_ITEM 20    /* per batch item: n_pred, n_true, 0, table-overflow flag, edge counts [16] (one per threshold) */
+#define MSAM_MATCH_EDGE 6     /* per edge: batch item, pred id, gt id, common pixels, pred area, gt area */
+/* pred int32 [B, H, W]; gt int32 [G, H, W] with G == B, or G == 1: every prediction against the same image.  Ids: any
+ * non-negative int32, 0 = background.  thresholds: HOST fp64 [T], 1 <= T <= 16.  Per batch item the device builds the full
+ * contingency table of (pred id, gt id) pairs (background included, exact int32 counts) in an open-addressing table of
+ * `capacity` slots (a power of two >= 1024, >= 2 x the distinct pairs of an item for short probe chains), sums object areas
+ * from it, counts the distinct non-zero ids, scores every pair of non-zero ids as (double) c / fmax((double) (area_p + area_g
+ * - c), 1e-7), counts per threshold the pairs with score >= t and appends those with score >= min(t) to ONE edge list (order
+ * unspecified).  result: int32 [MSAM_MATCH_HEADER + B * MSAM_MATCH_ITEM + max_edges * MSAM_MATCH_EDGE] on the device; when
+ * result[1] or an item's overflow flag is set, nothing was written out of bounds but the counts are not valid: enlarge and
+ * repeat.  workspace: the caller's, of the size the query returns (0 for bad B / capacity); initialised here.  It holds, each
+ * [B, capacity]: the pair keys uint64 (pred id << 32 | gt id; all-ones = empty), the pred-id table and the gt-id table int32
+ * (-1 = empty), then the int32 pair counts, pred areas and gt areas in the slots of their keys / ids.  Integer sums
+ * only: two runs give identical results.  No host synchronisation; three memsets and three kernels on `stream`. */
+int64_t msam_label_matching_workspace_bytes(int32_t B, int32_t capacity);
+int msam_label_matching(const int32_t* pred, const int32_t* gt, int32_t B, int32_t G, int32_t H, int32_t W,
+                        const double* thresholds, int32_t T, void* workspace, int64_t workspace_bytes, int32_t capacity,
+                        int32_t* result, int32_t max_edges, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Overlap of objects between consecutive slices:  merge_instance_segmentation_3d's edge extraction
  * (micro_sam/multi_dimensional_segmentation.py:356-363 -> elf.tracking compute_edges_from_overlap -> nifty.ground_truth.overlap;
  *  SURVEY.md 8(f) rank 3)

@@ -250,6 +250,8 @@ _PROTOS = {
     "msam_objfeat_accumulate": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "msam_objfeat_finish": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "msam_objfeat_project": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp]),
+    "msam_label_matching_workspace_bytes": (_i64, [_i32, _i32]),
+    "msam_label_matching": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(C.c_double), _i32, _vp, _i64, _i32, _vp, _i32, _vp]),
 }
 OPTIONAL = set()
 

@@ -1170,3 +1170,6 @@ def uncrop_bits(bits: torch.Tensor, crop_box, height: int, width: int) -> torch.
         _lib.check(lib.msam_uncrop_bits(bits[s:].data_ptr(), m, y1 - y0, x1 - x0, x0, y0, height, width, out[s:].data_ptr(),
                                         _lib.stream_ptr()), "msam_uncrop_bits")
     return out
+
+
+from ._matching import label_matching  # noqa: E402,F401  (defined in _matching.py, which uses _home / _need of this module)
