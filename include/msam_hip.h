@@ -838,6 +838,36 @@ int msam_objfeat_finish(const double* partial, const int32_t* chunk_start, const
                         int64_t* area_total, int32_t out_f64, void* out, void* stream);
 int msam_objfeat_project(const int64_t* labels, int64_t n, const int64_t* ids, int32_t n_ids, int32_t* index, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Label properties for the prompt-based evaluation (micro_sam/util.py:1283-1331 get_centers_and_bounding_boxes;
+ * csrc/labelprops.hip): exact squared Euclidean distance transform, per-object area / bounding box / coordinate sums / centre
+ * ------------------------------------------------------------------------------------------------- */
+#define MSAM_EDT_MAX_SIDE 32767
+/* mask: uint8 (mask_is_int32 = 0) or int32 (1) [H, W], non-zero = inside.  out: int32 [H, W] = the EXACT squared Euclidean
+ * distance of every pixel to the nearest zero pixel, 0 at zero pixels; a mask without any zero pixel yields INT32_MAX everywhere.
+ * 1 <= H, W <= 32767, so the largest real value, 2 * 32766^2, fits an int32 (and the intermediate column distance squared cannot
+ * overflow).  Separable: vertical distances per column, then per pixel the minimum over the row of (x - x')^2 + g(y, x')^2, scanned
+ * outwards from x until (x - x')^2 reaches the best value found.  workspace: the caller's, int32 [H, W] + int32 [3, ceil(H / 32), W]
+ * (the query returns 0 for bad sides).  Four kernels on `stream`, no synchronisation. */
+int64_t msam_edt_squared_workspace_bytes(int32_t H, int32_t W);
+int msam_edt_squared(const void* mask, int32_t mask_is_int32, int32_t H, int32_t W, int32_t* out, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+/* labels: int32 [H, W] (0 and negative values = background); ids: DEVICE int32 [N], N >= 1, positive, distinct, sorted ascending
+ * (checked on the device; the call waits for that one answer before it writes anything, and returns 1 when the check fails).
+ * Per id, in the order of ids:
+ *   area      int32 [N]     pixels of the object (0 for an id the image does not hold; then bbox = 0 and center = -1)
+ *   bbox      int32 [N, 4]  y0, x0, y1, x1 with exclusive ends (skimage regionprops.bbox)
+ *   coord_sum int64 [N, 2]  sums of the y and of the x coordinates (centroid = coord_sum / area)
+ *   center    int32 [N, 2]  (y, x) of the object's pixel with the largest squared distance to the nearest INNER BOUNDARY pixel of the
+ *                           label image (label != 0 and a 4-neighbour with another label, outside the image = 0); among equal
+ *                           distances the smallest raster index y * W + x.  NULL: not computed (no distance transform is run).
+ * workspace: the caller's; int32 [3, H, W] (column distances, squared distances, object index) + int32 [2, N] + four words + int32
+ * [3, ceil(H / 32), W].
+ * Integer atomics only: two runs give identical results. */
+int64_t msam_label_props_workspace_bytes(int32_t H, int32_t W, int32_t N);
+int msam_label_props(const int32_t* labels, int32_t H, int32_t W, const int32_t* ids, int32_t N, int32_t* area, int32_t* bbox,
+                     int64_t* coord_sum, int32_t* center, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

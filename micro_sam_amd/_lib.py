@@ -252,6 +252,10 @@ _PROTOS = {
     "msam_objfeat_project": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp]),
     "msam_label_matching_workspace_bytes": (_i64, [_i32, _i32]),
     "msam_label_matching": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(C.c_double), _i32, _vp, _i64, _i32, _vp, _i32, _vp]),
+    "msam_edt_squared_workspace_bytes": (_i64, [_i32, _i32]),
+    "msam_edt_squared": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
+    "msam_label_props_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "msam_label_props": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 OPTIONAL = set()
 

@@ -839,6 +839,73 @@ def compute_iou(mask1: np.ndarray, mask2: np.ndarray) -> float:
     return float(overlap) / (float(union) + 1e-7)
 
 
+def _labels_on_device(segmentation) -> torch.Tensor:
+    """A 2-d label image (numpy array or tensor) as a contiguous int32 tensor on the device the kernels run on."""
+    ndim = segmentation.ndim
+    if ndim != 2:
+        raise ValueError(f"Only 2-d label images are supported, got an input with {ndim} dimensions.")
+    device = _lib.require_gpu()
+    if torch.is_tensor(segmentation):
+        seg = segmentation
+    else:
+        seg = np.asarray(segmentation)
+        if seg.dtype.kind not in "iub" or (seg.size and int(seg.max()) > 2 ** 31 - 1):
+            raise ValueError(f"The label image must hold integer ids below 2^31, got {seg.dtype}.")
+        seg = torch.from_numpy(np.ascontiguousarray(seg.astype(np.int32, copy=False)))
+    return seg.to(device=device, dtype=torch.int32).contiguous()
+
+
+def get_centers_and_bounding_boxes(segmentation, mode: str = "v") -> Tuple[Dict[int, tuple], Dict[int, tuple]]:
+    """Reference util.py:1283-1331 on the device (``ops.label_props``, csrc/labelprops.hip): centre coordinates and bounding boxes
+    (y0, x0, y1, x1, exclusive ends) of the objects of a 2-d label image, as two dicts keyed by object id.  mode "v": the object's
+    pixel furthest from any inner boundary of the label image (always inside the object; among equally distant pixels the first in
+    raster order), as tuples of ints; mode "p": the centroid, as tuples of floats.  ``segmentation``: a numpy array or a tensor; one
+    device call and one copy back."""
+    assert mode in ["p", "v"], "Choose either 'p' for regionprops centroids or 'v' for distance-based centers"
+    from . import ops
+    props = ops.label_props(_labels_on_device(segmentation), centers=mode == "v")
+    n = int(props.ids.numel())
+    if n == 0:
+        return {}, {}
+    third = props.center if mode == "v" else props.area[:, None]
+    packed = torch.cat([props.ids[:, None].to(torch.int64), props.bbox.to(torch.int64), props.coord_sum, third.to(torch.int64)], dim=1).cpu().numpy()
+    ids, bbox = packed[:, 0].tolist(), packed[:, 1:5].tolist()
+    if mode == "v":
+        centers = [(int(y), int(x)) for y, x in packed[:, 7:9].tolist()]
+    else:
+        mean = packed[:, 5:7].astype(np.float64) / packed[:, 7:8].astype(np.float64)
+        centers = [(float(y), float(x)) for y, x in mean]
+    center_coordinates = {int(i): c for i, c in zip(ids, centers)}
+    bbox_coordinates = {int(i): tuple(int(v) for v in b) for i, b in zip(ids, bbox)}
+    assert len(bbox_coordinates) == len(center_coordinates), f"{len(bbox_coordinates)}, {len(center_coordinates)}"
+    return center_coordinates, bbox_coordinates
+
+
+def segmentation_to_one_hot(segmentation, segmentation_ids=None) -> torch.Tensor:
+    """Reference util.py:1356-1395: a label image -> float32 one-hot masks [N, 1, H, W].  Without ids N is the largest id and channel
+    k holds id k + 1.  With ids: they are sorted, objects not selected are dropped, and - the reference relabels the remaining
+    objects sequentially - the channels hold the selected ids that occur in the image in ascending order, followed by empty channels
+    for those that do not.  A numpy input gives a CPU tensor as in the reference; a tensor stays on its device.  The comparison runs
+    per channel against the id: no [max + 1, H, W] volume is built when ids are given."""
+    seg = segmentation if torch.is_tensor(segmentation) else torch.from_numpy(np.ascontiguousarray(np.asarray(segmentation).astype(np.int64)))
+    if segmentation_ids is None:
+        n_ids = int(seg.max()) if seg.numel() else 0
+        ids = torch.arange(1, n_ids + 1, device=seg.device, dtype=seg.dtype)
+    else:
+        msg = "No foreground objects were found."
+        segmentation_ids = segmentation_ids.cpu().numpy() if torch.is_tensor(segmentation_ids) else np.asarray(segmentation_ids)
+        if len(segmentation_ids) == 0 or 0 in segmentation_ids:
+            raise RuntimeError(msg)
+        n_ids = len(segmentation_ids)
+        ids = torch.from_numpy(np.unique(segmentation_ids).astype(np.int64)).to(device=seg.device, dtype=seg.dtype)
+    masks = seg[None] == ids.view(-1, *([1] * seg.dim()))
+    if segmentation_ids is not None:
+        masks = masks[masks.flatten(1).any(dim=1)]                       # relabel_sequential: only ids that occur keep a channel
+        if masks.shape[0] < n_ids:
+            masks = torch.cat([masks, torch.zeros((n_ids - masks.shape[0],) + tuple(seg.shape), dtype=torch.bool, device=seg.device)])
+    return masks.to(torch.float32).unsqueeze(1)
+
+
 # ------------------------------------------------------------------------------------------------ label image
 
 def _block_major_keys(h: int, w: int, block: int = 512) -> np.ndarray:
