@@ -868,6 +868,42 @@ int64_t msam_label_props_workspace_bytes(int32_t H, int32_t W, int32_t N);
 int msam_label_props(const int32_t* labels, int32_t H, int32_t W, const int32_t* ids, int32_t N, int32_t* area, int32_t* bbox,
                      int64_t* coord_sum, int32_t* center, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Slice-to-slice propagation of P objects at once (multi_dimensional_segmentation.segment_objects_in_volume; reference
+ * micro_sam/multi_dimensional_segmentation.py:105-233, prompt_based_segmentation.py:30-35, :84-115, :123-145; csrc/propagate.hip):
+ * what happens between two batched decodes, on bit masks in the layout msam_postprocess_masks writes - uint32 [P, ceil(H / 32), W],
+ * bit b of word [p][yw][x] = pixel (yw * 32 + b, x).  Bits of rows >= H in the last word row are IGNORED by every entry point and may
+ * hold anything.  1 <= P <= 65535, 1 <= H, W <= 32767.  No workspace, no allocation, no synchronisation; integer sums only, so two
+ * runs give the same bits.  A refusal returns non-zero with a message that names the entry point and leaves the outputs untouched.
+ * ------------------------------------------------------------------------------------------------- */
+#define MSAM_MASK_MAX_SIDE 32767
+#define MSAM_MASK_MAX_OBJECTS 65535
+/* masks: uint8 [P, H, W]; a pixel is set where the value == 1.  bits: the layout above, tail bits written as zeros.  One launch. */
+int msam_mask_pack(const uint8_t* masks, int32_t P, int32_t H, int32_t W, uint32_t* bits, void* stream);
+/* counts: int32 [P, 2] = (pixels set in both, pixels set in either), exact.  keep: uint8 [P] = !(iou < threshold) with
+ * iou = (double)overlap / ((double)union + 1e-7): util.compute_iou and the comparison of the walk, in the same fp64 arithmetic (two
+ * empty masks give 0; a NaN threshold keeps everything).  Three launches. */
+int msam_mask_iou_counts(const uint32_t* a, const uint32_t* b, int32_t P, int32_t H, int32_t W, double threshold, int32_t* counts,
+                         uint8_t* keep, void* stream);
+/* boxes: float32 [P, 4] XYXY in the model's input frame (input_h, input_w = the predictor's input_size), bit for bit the chain
+ * _compute_box_from_mask(mask, box_extension=...) -> ResizeLongestSide.apply_boxes -> float32: half-open bounding box, grown by
+ * box_extension pixels (>= 1) or by that fraction of the side lengths (< 1), clipped to the image, rounded half to even, scaled by
+ * input_w / W and input_h / H in fp64, rounded to fp32.  0 <= box_extension <= 1e9.  nonempty: uint8 [P]; an empty mask has a box of
+ * zeros and nonempty = 0.  `boxes` doubles as the integer accumulator of the bounding box.  Three launches. */
+int msam_mask_box_prompts(const uint32_t* bits, int32_t P, int32_t H, int32_t W, double box_extension, int32_t input_h, int32_t input_w,
+                          float* boxes, uint8_t* nonempty, void* stream);
+/* logits: float32 [P, 256, 256], the mask prompt of _compute_logits_from_mask: the binary mask resized to
+ * get_preprocess_shape(H, W, 256) with the antialiased triangle filter of F.interpolate(mode="bilinear", align_corners=False,
+ * antialias=True) (per axis: support max(in / out, 1), centre (i + 0.5) in / out, taps [max(int(c - s + 0.5), 0), min(int(c + s + 0.5), in)),
+ * weights normalised by their sum), zero-padded to the square; > 0.5 -> log((1 - 1e-3) / 1e-3), else log(1e-3 / (1 - 1e-3)).  fp32
+ * sums in a fixed order per pixel: a pixel whose exact value lies within about 1e-6 of 0.5 may fall on either side.  One launch. */
+int msam_mask_logits(const uint32_t* bits, int32_t P, int32_t H, int32_t W, float* logits, void* stream);
+/* label: int32 [H, W], updated to max(label, ids[p]) wherever bit p is set and keep[p] != 0 (keep NULL: every object).  ids: int32 [P]
+ * on the device.  Composing objects with "label[mask_p] = id_p" in ascending id order equals this maximum for non-negative labels, so
+ * slices can be painted as they are finished.  One launch. */
+int msam_paint_max(const uint32_t* bits, const int32_t* ids, const uint8_t* keep, int32_t P, int32_t H, int32_t W, int32_t* label,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -688,3 +688,143 @@ def segment_mask_in_volume(segmentation: np.ndarray, predictor, image_embeddings
                 if gap % 2 == 0:          # the middle slice is equally far from both ends: union of its neighbours
                     fill_between(z_mid, z_mid - 1, z_mid + 1)
     return segmentation, (z_min, z_max)
+
+
+# ------------------------------------------------------------------------------------------ all objects of a volume at once
+
+def _can_propagate_on_device(predictor, image_embeddings, use_points: bool) -> bool:
+    """The device path of ``segment_objects_in_volume`` covers box / mask projections on untiled 3-d embeddings with the default
+    (16-bit) decoder on a GPU.  Point projections sample their points on the host (distance transform + peak search), tiled embeddings
+    route every object to a tile of its own, and the strict / split16 decoder has not been run with a batch of mask prompts: all three
+    take the per-object loop."""
+    if use_points or image_embeddings is None or image_embeddings.get("input_size") is None:
+        return False
+    features = image_embeddings["features"]
+    if getattr(features, "ndim", 0) != 5:
+        return False
+    model = getattr(predictor, "model", None)
+    if model is None or not hasattr(model, "decode") or getattr(model, "reference_formulation", False):
+        return False
+    return str(predictor.device).startswith("cuda") and torch.cuda.is_available()
+
+
+def _objects_per_object_loop(predictor, image_embeddings, seeds, seed_slices, ids, iou_threshold, projection, box_extension, verbose):
+    """N calls of ``segment_mask_in_volume``, composed in ascending id order."""
+    features = image_embeddings["features"]
+    Z = (features if image_embeddings["input_size"] is not None else features["0"]).shape[0]          # (tiled: the slices of a tile)
+    H, W = seeds.shape[1:]
+    labels = np.zeros((Z, H, W), dtype=np.int32)
+    ranges = np.zeros((len(ids), 2), dtype=np.int64)
+    for n in np.argsort(ids, kind="stable"):
+        seg = np.zeros((Z, H, W), dtype=np.uint8)
+        seg[seed_slices[n]] = seeds[n] == 1
+        seg, ranges[n] = segment_mask_in_volume(seg, predictor, image_embeddings, np.array(int(seed_slices[n])), stop_lower=False,
+                                                stop_upper=False, iou_threshold=iou_threshold, projection=projection,
+                                                box_extension=box_extension, verbose=verbose)
+        labels[seg == 1] = ids[n]
+    return labels, ranges
+
+
+@torch.no_grad()
+def _objects_on_device(predictor, image_embeddings, seeds, seed_slices, ids, iou_threshold, use_box, use_mask, box_extension,
+                       batch_size, verbose):
+    from . import ops
+    dev = torch.device(predictor.device)
+    Z = image_embeddings["features"].shape[0]
+    N, H, W = seeds.shape
+    input_size = tuple(int(v) for v in image_embeddings["input_size"])
+    model = predictor.model
+    labels = torch.zeros((Z, H, W), dtype=torch.int32, device=dev)
+    ranges = np.stack([seed_slices, seed_slices], axis=1).astype(np.int64)
+    if N == 0:
+        return labels, ranges
+    seeds_dev = seeds if torch.is_tensor(seeds) else torch.from_numpy(np.ascontiguousarray(seeds))
+    seeds_dev = (seeds_dev.to(dev) == 1).view(torch.uint8).contiguous()
+    ids_dev = torch.as_tensor(np.asarray(ids, dtype=np.int32), device=dev)
+    step = 65535
+    seed_bits = torch.cat([ops.pack_bits(seeds_dev[s:s + step]) for s in range(0, N, step)])
+    del seeds_dev
+    seed_parts = [ops.mask_box_prompts(seed_bits[s:s + step], H, W, input_size, box_extension) for s in range(0, N, step)]
+    seed_nonempty = torch.cat([p[0] for p in seed_parts])
+    seed_boxes = torch.cat([p[1] for p in seed_parts])
+    for z in np.unique(seed_slices):
+        idx = torch.as_tensor(np.flatnonzero(seed_slices == z), device=dev)
+        for s in range(0, len(idx), step):
+            ops.paint_max(seed_bits[idx[s:s + step]], ids_dev[idx[s:s + step]], labels[z])
+    seeded = seed_nonempty.cpu().numpy().astype(bool)               # the one copy before the sweeps: an empty seed walks nowhere
+    batch_size = max(1, min(int(batch_size), step))
+    for direction in (1, -1):
+        cur_bits, cur_boxes = seed_bits.clone(), seed_boxes.clone()
+        alive = seeded.copy()
+        for z in (range(1, Z) if direction == 1 else range(Z - 2, -1, -1)):
+            active = np.flatnonzero(alive & ((seed_slices < z) if direction == 1 else (seed_slices > z)))
+            if len(active) == 0:
+                continue
+            if verbose:
+                print(f"Segmenting slice {z}: {len(active)} objects")
+            util.set_precomputed(predictor, image_embeddings, i=z)
+            flags = []
+            for s in range(0, len(active), batch_size):
+                idx = torch.as_tensor(active[s:s + batch_size], device=dev)
+                prev = cur_bits[idx]
+                logits = ops.mask_logits(prev, H, W) if use_mask else None
+                low, _ = model.decode(predictor.features, None, None, cur_boxes[idx] if use_box else None, logits, False)
+                new = ops.postprocess_masks(low.reshape(-1, 256, 256), predictor.input_size, predictor.original_size,
+                                            model.mask_threshold, 1.0)["bits"]
+                _, keep = ops.mask_iou_counts(prev, new, H, W, iou_threshold)
+                ops.paint_max(new, ids_dev[idx], labels[z], keep)
+                nonempty, boxes = ops.mask_box_prompts(new, H, W, input_size, box_extension)
+                cur_bits[idx] = new
+                cur_boxes[idx] = boxes
+                flags.append(torch.stack([keep, nonempty]))
+            keep, nonempty = torch.cat(flags, dim=1).cpu().numpy().astype(bool)      # the slice's one copy to the host
+            ranges[active[keep], 0 if direction == -1 else 1] = z
+            alive[active] = keep & nonempty
+    return labels, ranges
+
+
+def segment_objects_in_volume(predictor, image_embeddings, seeds, seed_slices, ids, iou_threshold: float, projection,
+                              box_extension: float = 0.0, batch_size: int = 64, return_device: bool = False,
+                              verbose: bool = False):
+    """All objects of a volume carried through it at once: exactly N independent calls of
+    ``segment_mask_in_volume(seg_n, ..., segmented_slices=np.array(seed_slices[n]), stop_lower=False, stop_upper=False, ...)``, where
+    ``seg_n`` holds ``seeds[n] == 1`` in slice ``seed_slices[n]``, their results written into one volume in ascending id order (where
+    objects overlap the larger id stays, as ``final[seg_n == 1] = ids[n]`` in that order leaves it).
+
+    ``seeds`` [N, H, W] (array or tensor; a pixel belongs to the object where the value == 1), ``seed_slices`` [N], ``ids`` [N]
+    ascending positive labels.  Returns (labels int32 [Z, H, W], ranges int64 [N, 2]); ``ranges[n]`` is the (z_min, z_max) of call n.
+    ``return_device=True`` leaves the labels on the device (``evaluation.mean_segmentation_accuracy`` scores them there).
+
+    Box / mask projections ("mask", "box", dicts with ``use_points=False``) on untiled 3-d embeddings run on the device: two sweeps
+    over z (up, then down); at slice z every object that is still alive and whose seed lies on the far side is prompted from its bit
+    mask of the neighbouring slice (``ops.mask_box_prompts`` / ``ops.mask_logits``), all of them decoded in batches of ``batch_size``
+    against the slice's embedding, gated by the IoU with the previous mask (``ops.mask_iou_counts``: the fp64 expression of
+    ``util.compute_iou``) and painted (``ops.paint_max``).  One small copy to the host per slice - the keep / nonempty flags - compacts
+    the active set; no mask reaches the host.  The prompts equal the host's except where the resized mask lies within rounding of
+    0.5 (a handful of pixels of a mask prompt: DESIGN.md).
+
+    An object whose accepted mask is empty has that (empty) slice counted in its range and stops.  For ``iou_threshold > 0`` that is
+    the reference: an empty mask has IoU 0 with anything and is never accepted.  For ``iou_threshold <= 0`` the reference would go on
+    and decode without a box (or, for "box", without any prompt, which this decoder refuses); that is not reproduced here.
+
+    Point projections, tiled embeddings and the strict / split16 decoder run the per-object loop itself."""
+    use_box, use_mask, use_points, _ = _validate_projection(projection)
+    seed_slices = np.asarray(seed_slices, dtype=np.int64).reshape(-1)
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    if seeds.ndim != 3 or len(seed_slices) != seeds.shape[0] or len(ids) != seeds.shape[0]:
+        raise ValueError(f"seeds [N, H, W], seed_slices [N] and ids [N] are needed, got {tuple(seeds.shape)}, {len(seed_slices)}, {len(ids)}")
+    if len(ids) and (ids.min() <= 0 or ids.max() >= 2 ** 31 or (np.diff(ids) <= 0).any()):
+        raise ValueError("ids must be positive, ascending and below 2^31")
+    Z = image_embeddings["features"].shape[0] if image_embeddings.get("input_size") is not None else None      # (tiled: checked per call)
+    if Z is not None and len(seed_slices) and (seed_slices.min() < 0 or seed_slices.max() >= Z):
+        raise ValueError(f"seed_slices must lie in [0, {Z})")
+    if _can_propagate_on_device(predictor, image_embeddings, use_points):
+        if not (use_box or use_mask):
+            raise ValueError("micro_sam_amd: a projection needs a box, a mask and / or points")
+        labels, ranges = _objects_on_device(predictor, image_embeddings, seeds, seed_slices, ids, iou_threshold, use_box, use_mask,
+                                            box_extension, batch_size, verbose)
+        return (labels if return_device else labels.cpu().numpy()), ranges
+    seeds_host = seeds.cpu().numpy() if torch.is_tensor(seeds) else np.asarray(seeds)
+    labels, ranges = _objects_per_object_loop(predictor, image_embeddings, seeds_host, seed_slices, ids, iou_threshold, projection,
+                                              box_extension, verbose)
+    return (torch.from_numpy(labels).to(predictor.device) if return_device else labels), ranges
