@@ -867,6 +867,26 @@ int msam_edt_squared(const void* mask, int32_t mask_is_int32, int32_t H, int32_t
 int64_t msam_label_props_workspace_bytes(int32_t H, int32_t W, int32_t N);
 int msam_label_props(const int32_t* labels, int32_t H, int32_t W, const int32_t* ids, int32_t N, int32_t* area, int32_t* bbox,
                      int64_t* coord_sum, int32_t* center, void* workspace, int64_t workspace_bytes, void* stream);
+/* Training targets of the convolutional decoder: torch_em's PerObjectDistanceTransform restated (torch_em is
+ * not pinned).  labels: int32 [H, W], objects are the labels 1..N, every other value (0, negative, above N) is background and is never
+ * used as an index.  out: float32 [3, H, W] = foreground (0 / 1), centre distance, boundary distance; the two distance planes hold `fill`
+ * on the background.  Per object o (label o + 1): center int32 [N, 2] (y, x), dmax2 int32 [N], bbox int32 [N, 4] (y0, x0, y1, x1,
+ * exclusive ends); a label the image does not hold gets bbox 0, center -1, dmax2 0.
+ *   boundary pixel: an object pixel with a 4-neighbour INSIDE the image of another value (find_boundaries(mode="inner"); NOT the rule
+ *                   of msam_label_props, which counts the outside of the image as label 0);
+ *   d2            : exact squared distance to the nearest boundary pixel of the image (one transform for all objects; on an object's
+ *                   pixels equal to the transform of the boundaries cropped to its bounding box); dmax2[o] = max of d2 over o, 0 when
+ *                   the image has no boundary pixel at all (it then holds one object, whose boundary plane is 1);
+ *   centre        : the centroid rounded half to even per axis (exact, from the coordinate sums and the area); when that pixel is not
+ *                   of o and correct_centers = 1, the first pixel of o in raster order with d2 == dmax2[o];
+ *   centre plane  : sqrt((y - cy)^2 + (x - cx)^2) / (R + 1e-7), R = the largest distance from the centre to a pixel of the bounding box;
+ *   boundary plane: 1 - sqrt(d2) / (sqrt(dmax2[o]) + 1e-7).
+ * Integers are exact and integer atomics only, so two runs agree bit for bit; the floats are fp32 from exact integers.  N = 0 writes
+ * foreground 0 and `fill`.  workspace: the caller's, 16-byte aligned: int32 [2, H, W] rounded up to 16 bytes + 44 bytes per object +
+ * int32 [3, ceil(H / 32), W] (the query returns 0 for bad sides or N < 0).  Kernels on `stream`, no synchronisation. */
+int64_t msam_distance_targets_workspace_bytes(int32_t H, int32_t W, int32_t N);
+int msam_distance_targets(const int32_t* labels, int32_t H, int32_t W, int32_t N, int32_t correct_centers, float fill, float* out,
+                          int32_t* center, int32_t* dmax2, int32_t* bbox, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Slice-to-slice propagation of P objects at once (multi_dimensional_segmentation.segment_objects_in_volume; reference

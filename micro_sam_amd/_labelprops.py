@@ -1,6 +1,7 @@
-"""``ops.edt_squared`` and ``ops.label_props``: the Python side of csrc/labelprops.hip (msam_edt_squared, msam_label_props).  Defined here
-and re-exported by micro_sam_amd/ops.py with the boundary checks of the other wrappers (``ops._home`` / ``ops._t`` / ``ops._need``);
-tests/test_gpu_labelprops.py runs them on the device."""
+"""``ops.edt_squared``, ``ops.label_props`` and ``ops.distance_targets``: the Python side of csrc/labelprops.hip (msam_edt_squared,
+msam_label_props, msam_distance_targets).  Defined here and re-exported by micro_sam_amd/ops.py with the boundary checks of the other
+wrappers (``ops._home`` / ``ops._t`` / ``ops._need``); tests/test_gpu_labelprops.py and tests/test_gpu_distance_targets.py run them on the
+device."""
 from __future__ import annotations
 
 from typing import Any, Dict, NamedTuple, Optional
@@ -23,6 +24,15 @@ class LabelProps(NamedTuple):
     bbox: torch.Tensor
     coord_sum: torch.Tensor
     center: Optional[torch.Tensor]
+
+
+class DistanceTargets(NamedTuple):
+    """``out`` float32 [3, H, W] (foreground, centre distance, boundary distance) and, per object 1..N: ``center`` int32 [N, 2] (y, x),
+    ``dmax2`` int32 [N] (the largest squared boundary distance), ``bbox`` int32 [N, 4] (y0, x0, y1, x1, exclusive ends).  All on the device."""
+    out: torch.Tensor
+    center: torch.Tensor
+    dmax2: torch.Tensor
+    bbox: torch.Tensor
 
 
 def _workspace(dev: torch.device, nbytes: int) -> torch.Tensor:
@@ -87,3 +97,28 @@ def label_props(labels: torch.Tensor, ids: Optional[torch.Tensor] = None, center
                                     None if center is None else center.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
                "msam_label_props")
     return LabelProps(ids, area, bbox, coord_sum, center)
+
+
+def distance_targets(labels: torch.Tensor, n_objects: Optional[int] = None, correct_centers: bool = True, fill: float = 1.0) -> DistanceTargets:
+    """The training targets of the convolutional decoder on the device (msam_distance_targets; torch_em's ``PerObjectDistanceTransform``
+    restated, UNPINNED - torch_em is not available; definitions in include/msam_hip.h and DESIGN.md 8.4): labels int32 [H, W] whose
+    objects are the consecutive labels 1..``n_objects`` (every other value is background; None: the maximum of the labels, which costs one
+    synchronisation) -> ``DistanceTargets``.  Background pixels hold ``fill`` in the two distance planes.  Integer work is exact and
+    two calls agree bit for bit."""
+    from . import ops
+    dev = ops._home("labels", labels)
+    h, w = _image("labels", labels, torch.int32, dev)
+    n = max(int(labels.max()), 0) if n_objects is None else int(n_objects)
+    ops._need(0 <= n < 1 << 31, f"n_objects must be in [0, 2^31), got {n}")
+    ops._need(fill == fill, "fill is NaN")
+    out = torch.empty((3, h, w), dtype=torch.float32, device=dev)
+    center = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    dmax2 = torch.empty(n, dtype=torch.int32, device=dev)
+    bbox = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    need = int(lib.msam_distance_targets_workspace_bytes(h, w, n))
+    ws = _workspace(dev, need)
+    _lib.check(lib.msam_distance_targets(labels.data_ptr(), h, w, n, int(bool(correct_centers)), float(fill), out.data_ptr(),
+                                         center.data_ptr() if n else None, dmax2.data_ptr() if n else None, bbox.data_ptr() if n else None,
+                                         ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "msam_distance_targets")
+    return DistanceTargets(out, center, dmax2, bbox)

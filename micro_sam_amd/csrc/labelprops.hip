@@ -16,6 +16,11 @@
 //            pre-summed, then integer atomics per run: area, bounding box (min / max), coordinate sums (64-bit adds), and the maximum
 //            of d2 per object.
 //   centre : per pixel that reaches its object's maximum: atomicMin of the raster index - ties go to the first pixel in raster order.
+//
+// msam_distance_targets (the training targets of torch_em's PerObjectDistanceTransform, restated in DESIGN.md section 8.4) turns the same
+// passes towards labels 1..N: the zero pixels are scikit-image's find_boundaries(mode="inner") - only neighbours INSIDE the image count -,
+// the object index is the label itself, and one pixel-parallel pass writes the foreground, centre-distance and boundary-distance planes
+// from a 16-byte record per object.
 #include "common.h"
 #include "../../include/msam_hip.h"
 
@@ -32,16 +37,25 @@ constexpr int EDT_SEG = 32;                                           // rows pe
 constexpr int LP_PER = 8;
 constexpr int LP_NONE = 0x7fffffff;
 
-enum { SRC_U8 = 0, SRC_I32 = 1, SRC_LABELS = 2 };
+enum { SRC_U8 = 0, SRC_I32 = 1, SRC_LABELS = 2, SRC_INNER = 3 };
 
-// is pixel (y, x) a zero pixel of the distance transform?
+// labels 1..n are objects; every other value (0, negative, above n) is background and is never used as an index
+MSAM_DEVINL bool lp_is_object(int lab, int n) { return (unsigned)(lab - 1) < (unsigned)n; }
+
+// is pixel (y, x) a zero pixel of the distance transform?  nmax: the largest object label (SRC_INNER only)
 template <int SRC>
-MSAM_DEVINL bool edt_is_zero(const void* __restrict__ src, int H, int W, int y, int x) {
+MSAM_DEVINL bool edt_is_zero(const void* __restrict__ src, int H, int W, int nmax, int y, int x) {
     const size_t p = (size_t)y * W + x;
     if (SRC == SRC_U8) return ((const unsigned char*)src)[p] == 0;
     if (SRC == SRC_I32) return ((const int*)src)[p] == 0;
     const int* __restrict__ lab = (const int*)src;
     const int c = lab[p];
+    if (SRC == SRC_INNER) {                                            // an object pixel with another value next to it INSIDE the image
+        if (!lp_is_object(c, nmax)) return false;
+        auto differs = [&](int v) { return (lp_is_object(v, nmax) ? v : 0) != c; };
+        return (y > 0 && differs(lab[p - W])) || (y + 1 < H && differs(lab[p + W])) || (x > 0 && differs(lab[p - 1])) ||
+               (x + 1 < W && differs(lab[p + 1]));
+    }
     if (c == 0) return false;
     const int up = y > 0 ? lab[p - W] : 0, down = y + 1 < H ? lab[p + W] : 0;
     const int left = x > 0 ? lab[p - 1] : 0, right = x + 1 < W ? lab[p + 1] : 0;
@@ -51,14 +65,15 @@ MSAM_DEVINL bool edt_is_zero(const void* __restrict__ src, int H, int W, int y, 
 // first / last zero pixel of every (segment of EDT_SEG rows, column): top = rows from the segment's first row down to its first zero
 // pixel, bot = rows from its last zero pixel down to the segment's last row; EDT_GINF when the segment has none
 template <int SRC>
-__global__ __launch_bounds__(64) void edt_segment_kernel(const void* __restrict__ src, int H, int W, int* __restrict__ top, int* __restrict__ bot) {
+__global__ __launch_bounds__(64) void edt_segment_kernel(const void* __restrict__ src, int H, int W, int nmax, int* __restrict__ top,
+                                                         int* __restrict__ bot) {
     const int x = blockIdx.x * 64 + threadIdx.x;
     if (x >= W) return;
     const int s = blockIdx.y, y0 = s * EDT_SEG, y1 = y0 + EDT_SEG < H ? y0 + EDT_SEG : H;
     int first = EDT_GINF, last = EDT_GINF;
 #pragma unroll 4
     for (int y = y0; y < y1; ++y)
-        if (edt_is_zero<SRC>(src, H, W, y, x)) {
+        if (edt_is_zero<SRC>(src, H, W, nmax, y, x)) {
             if (first == EDT_GINF) first = y - y0;
             last = y1 - 1 - y;
         }
@@ -90,7 +105,7 @@ __global__ __launch_bounds__(64) void edt_carry_kernel(int H, int W, int S, cons
 
 // one thread per (segment, column): the two sweeps of the column pass inside the segment, started from the distances carried in
 template <int SRC>
-__global__ __launch_bounds__(64) void edt_column_kernel(const void* __restrict__ src, int H, int W, const int* __restrict__ above,
+__global__ __launch_bounds__(64) void edt_column_kernel(const void* __restrict__ src, int H, int W, int nmax, const int* __restrict__ above,
                                                         const int* __restrict__ below, int* __restrict__ g) {
     const int x = blockIdx.x * 64 + threadIdx.x;
     if (x >= W) return;
@@ -99,7 +114,7 @@ __global__ __launch_bounds__(64) void edt_column_kernel(const void* __restrict__
     if (cur != EDT_GINF) --cur;                                        // (the value of the row above the segment)
 #pragma unroll 4
     for (int y = y0; y < y1; ++y) {
-        cur = edt_is_zero<SRC>(src, H, W, y, x) ? 0 : (cur == EDT_GINF ? EDT_GINF : cur + 1);
+        cur = edt_is_zero<SRC>(src, H, W, nmax, y, x) ? 0 : (cur == EDT_GINF ? EDT_GINF : cur + 1);
         g[(size_t)y * W + x] = cur;
     }
     cur = below[(size_t)s * W + x];
@@ -119,9 +134,10 @@ MSAM_DEVINL unsigned edt_take(unsigned best, int dx, int a, int b) {
     return cand < best ? cand : best;
 }
 
-// FG_ONLY: pixels whose label is 0 get 0 (the label properties never read them)
-template <bool FG_ONLY>
-__global__ __launch_bounds__(256) void edt_row_kernel(const int* __restrict__ g, const int* __restrict__ labels, int W, int* __restrict__ out) {
+// SKIP = 1: pixels whose label is 0 get 0 (the label properties never read them); SKIP = 2: every pixel that is no object 1..nmax
+template <int SKIP>
+__global__ __launch_bounds__(256) void edt_row_kernel(const int* __restrict__ g, const int* __restrict__ labels, int W, int nmax,
+                                                      int* __restrict__ out) {
     __shared__ int sg[EDT_TILE + 2 * EDT_HALO];
     const int y = blockIdx.y, x0 = blockIdx.x * EDT_TILE;
     const int* __restrict__ grow = g + (size_t)y * W;
@@ -133,7 +149,8 @@ __global__ __launch_bounds__(256) void edt_row_kernel(const int* __restrict__ g,
     const int x = x0 + threadIdx.x;
     if (x >= W) return;
     const size_t p = (size_t)y * W + x;
-    if (FG_ONLY && labels[p] == 0) { out[p] = 0; return; }
+    if (SKIP == 1 && labels[p] == 0) { out[p] = 0; return; }
+    if (SKIP == 2 && !lp_is_object(labels[p], nmax)) { out[p] = 0; return; }
     const int c = EDT_HALO + threadIdx.x;
     const int gc = sg[c];
     unsigned best = gc == EDT_GINF ? EDT_INF : (unsigned)(gc * gc);
@@ -170,7 +187,9 @@ __global__ __launch_bounds__(256) void lp_init_kernel(int n, int* __restrict__ a
     maxd[o] = -1; first[o] = LP_NONE;
 }
 
-// dist == nullptr: no centres wanted (index and maxd are not written)
+// dist == nullptr: no centres wanted (index and maxd are not written).  CONSEC: the objects are the labels 1..n themselves (object index =
+// label - 1; ids and index are not used)
+template <bool CONSEC>
 __global__ __launch_bounds__(256) void lp_stats_kernel(const int* __restrict__ labels, const int* __restrict__ dist, int W,
                                                        const int* __restrict__ ids, int n, int* __restrict__ index, int* __restrict__ area,
                                                        int* __restrict__ bbox, u64* __restrict__ sums, int* __restrict__ maxd) {
@@ -191,21 +210,23 @@ __global__ __launch_bounds__(256) void lp_stats_kernel(const int* __restrict__ l
     const int xe = xb + LP_PER < W ? xb + LP_PER : W;
     for (int x = xb; x < xe; ++x) {
         const int lab = labels[row + x];
-        const int o = lab == prev_lab ? prev_o : (lab > 0 ? lp_find(ids, n, lab) : -1);
+        const int o = CONSEC ? (lp_is_object(lab, n) ? lab - 1 : -1) : (lab == prev_lab ? prev_o : (lab > 0 ? lp_find(ids, n, lab) : -1));
         prev_lab = lab; prev_o = o;
         const int d = (dist && o >= 0) ? dist[row + x] : 0;
-        if (dist) index[row + x] = o;
+        if (!CONSEC && dist) index[row + x] = o;
         if (o == run_o) { ++run_n; run_d = d > run_d ? d : run_d; }
         else { flush(run_o, run_x, run_n, run_d); run_o = o; run_x = x; run_n = 1; run_d = d; }
     }
     flush(run_o, run_x, run_n, run_d);
 }
 
-__global__ __launch_bounds__(256) void lp_center_kernel(const int* __restrict__ index, const int* __restrict__ dist, int npx,
+// CONSEC: index is the label image itself and n the largest label
+template <bool CONSEC>
+__global__ __launch_bounds__(256) void lp_center_kernel(const int* __restrict__ index, const int* __restrict__ dist, int npx, int n,
                                                         const int* __restrict__ maxd, int* __restrict__ first) {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= npx) return;
-    const int o = index[p];
+    const int o = CONSEC ? (lp_is_object(index[p], n) ? index[p] - 1 : -1) : index[p];
     if (o >= 0 && dist[p] == maxd[o]) atomicMin(&first[o], p);
 }
 
@@ -226,19 +247,114 @@ bool lp_side_ok(int32_t H, int32_t W) { return H > 0 && W > 0 && H <= MSAM_EDT_M
 int64_t edt_carry_ints(int H, int W) { return (int64_t)((H + EDT_SEG - 1) / EDT_SEG) * W * 3; }   // top, bot / below, above per (segment, column)
 
 template <int SRC>
-void edt_launch(const void* src, const int* labels, int H, int W, int* g, int* carry, int* out, hipStream_t s) {
+void edt_launch(const void* src, const int* labels, int H, int W, int nmax, int* g, int* carry, int* out, hipStream_t s) {
     const int S = (H + EDT_SEG - 1) / EDT_SEG;
     int* top = carry;
     int* bot = top + (size_t)S * W;
     int* above = bot + (size_t)S * W;
     const dim3 cols((unsigned)((W + 63) / 64), (unsigned)S);
-    hipLaunchKernelGGL((edt_segment_kernel<SRC>), cols, dim3(64), 0, s, src, H, W, top, bot);
+    hipLaunchKernelGGL((edt_segment_kernel<SRC>), cols, dim3(64), 0, s, src, H, W, nmax, top, bot);
     hipLaunchKernelGGL(edt_carry_kernel, dim3((unsigned)((W + 63) / 64)), dim3(64), 0, s, H, W, S, (const int*)top, bot, above);
-    hipLaunchKernelGGL((edt_column_kernel<SRC>), cols, dim3(64), 0, s, src, H, W, (const int*)above, (const int*)bot, g);
+    hipLaunchKernelGGL((edt_column_kernel<SRC>), cols, dim3(64), 0, s, src, H, W, nmax, (const int*)above, (const int*)bot, g);
     const dim3 grid((unsigned)((W + EDT_TILE - 1) / EDT_TILE), (unsigned)H);
-    if (SRC == SRC_LABELS) hipLaunchKernelGGL((edt_row_kernel<true>), grid, dim3(256), 0, s, (const int*)g, labels, W, out);
-    else hipLaunchKernelGGL((edt_row_kernel<false>), grid, dim3(256), 0, s, (const int*)g, labels, W, out);
+    if (SRC == SRC_INNER) hipLaunchKernelGGL((edt_row_kernel<2>), grid, dim3(256), 0, s, (const int*)g, labels, W, nmax, out);
+    else if (SRC == SRC_LABELS) hipLaunchKernelGGL((edt_row_kernel<1>), grid, dim3(256), 0, s, (const int*)g, labels, W, nmax, out);
+    else hipLaunchKernelGGL((edt_row_kernel<0>), grid, dim3(256), 0, s, (const int*)g, labels, W, nmax, out);
 }
+
+// ---- msam_distance_targets: what the final pass reads per object
+struct __attribute__((aligned(16))) DtObject {
+    int cy, cx;                                                        // the centre
+    float bden, cden;                                                  // denominators of the boundary and the centre channel
+};
+
+constexpr int DT_PER = 4;                                              // pixels per thread of the vector form of the final pass
+
+MSAM_DEVINL int dt_round_half_even(u64 s, u64 a) {                     // s / a rounded half to even, exactly
+    const u64 q = s / a, r = s - q * a;
+    if (2 * r < a) return (int)q;
+    if (2 * r > a) return (int)q + 1;
+    return (int)(q + (q & 1));
+}
+
+// The normalisation of the centre channel - the ONE place that fixes it.  torch_em divides the distances to the centre by their maximum
+// over the object's bounding-box CROP, taken before the crop is masked to the object; the distance to a point is convex, so that maximum
+// lies on one of the crop's four corner pixels: R^2 = max(cy - y0, y1 - 1 - cy)^2 + max(cx - x0, x1 - 1 - cx)^2.
+MSAM_DEVINL int dt_center_norm2(int cy, int cx, int y0, int x0, int y1, int x1) {
+    const int dy = cy - y0 > y1 - 1 - cy ? cy - y0 : y1 - 1 - cy;
+    const int dx = cx - x0 > x1 - 1 - cx ? cx - x0 : x1 - 1 - cx;
+    return dy * dy + dx * dx;                                          // <= 2 * 32766^2 < 2^31
+}
+
+__global__ __launch_bounds__(256) void dt_finish_kernel(const int* __restrict__ labels, int W, int n, int correct, const int* __restrict__ area,
+                                                        const u64* __restrict__ sums, const int* __restrict__ maxd, const int* __restrict__ first,
+                                                        int* __restrict__ bbox, int* __restrict__ center, int* __restrict__ dmax2,
+                                                        DtObject* __restrict__ table) {
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o >= n) return;
+    DtObject t;
+    if (area[o] == 0) {                                                // a label the image does not hold (the final pass never reads its record)
+        bbox[4 * o] = 0; bbox[4 * o + 1] = 0;
+        center[2 * o] = -1; center[2 * o + 1] = -1; dmax2[o] = 0;
+        t.cy = -1; t.cx = -1; t.bden = INFINITY; t.cden = INFINITY;
+        table[o] = t;
+        return;
+    }
+    const u64 a = (u64)area[o];
+    int cy = dt_round_half_even(sums[2 * o], a), cx = dt_round_half_even(sums[2 * o + 1], a);
+    if (correct && labels[(size_t)cy * W + cx] != o + 1) {             // the centroid lies outside: the first pixel of maximal distance
+        const int p = first[o];
+        cy = p / W; cx = p - cy * W;
+    }
+    // an image without any boundary pixel (EDT_INF everywhere) holds one object: its boundary channel is 1
+    const int dm = (unsigned)maxd[o] == EDT_INF ? 0 : maxd[o];
+    center[2 * o] = cy; center[2 * o + 1] = cx; dmax2[o] = dm;
+    t.cy = cy; t.cx = cx;
+    t.bden = dm == 0 ? INFINITY : sqrtf((float)dm) + 1e-7f;            // d2 / inf = 0: the channel is 1 on such an object
+    t.cden = sqrtf((float)dt_center_norm2(cy, cx, bbox[4 * o], bbox[4 * o + 1], bbox[4 * o + 2], bbox[4 * o + 3])) + 1e-7f;
+    table[o] = t;
+}
+
+// V pixels per thread, consecutive in raster order (V = 4: 16-byte loads and stores; npx is then a multiple of 4 and every plane 16-byte
+// aligned).  table == nullptr: no objects, d2 is not read
+template <int V>
+__global__ __launch_bounds__(256) void dt_write_kernel(const int* __restrict__ labels, const int* __restrict__ d2, unsigned npx, unsigned W, int n,
+                                                       const DtObject* __restrict__ table, float fill, float* __restrict__ out) {
+    const unsigned p0 = (blockIdx.x * 256u + threadIdx.x) * V;
+    if (p0 >= npx) return;
+    int lab[V], dd[V];
+    float fg[V], ce[V], bd[V];
+    if (V == 4) {
+        const uint4 l = *(const uint4*)(labels + p0);
+        lab[0] = (int)l.x; lab[1] = (int)l.y; lab[2] = (int)l.z; lab[3] = (int)l.w;
+        if (table) { const uint4 d = *(const uint4*)(d2 + p0); dd[0] = (int)d.x; dd[1] = (int)d.y; dd[2] = (int)d.z; dd[3] = (int)d.w; }
+    } else {
+        lab[0] = labels[p0];
+        if (table) dd[0] = d2[p0];
+    }
+    unsigned y = p0 / W, x = p0 - y * W;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        fg[i] = 0.f; ce[i] = fill; bd[i] = fill;
+        if (table && lp_is_object(lab[i], n)) {
+            const DtObject t = table[lab[i] - 1];
+            const int dy = (int)y - t.cy, dx = (int)x - t.cx;
+            fg[i] = 1.f;
+            ce[i] = sqrtf((float)(dy * dy + dx * dx)) / t.cden;
+            bd[i] = 1.f - sqrtf((float)dd[i]) / t.bden;
+        }
+        if (++x == W) { x = 0; ++y; }
+    }
+    if (V == 4) {
+        *(float4*)(out + p0) = make_float4(fg[0], fg[1], fg[2], fg[3]);
+        *(float4*)(out + (size_t)npx + p0) = make_float4(ce[0], ce[1], ce[2], ce[3]);
+        *(float4*)(out + 2 * (size_t)npx + p0) = make_float4(bd[0], bd[1], bd[2], bd[3]);
+    } else {
+        out[p0] = fg[0]; out[(size_t)npx + p0] = ce[0]; out[2 * (size_t)npx + p0] = bd[0];
+    }
+}
+
+int64_t dt_pixel_bytes(int H, int W) { return ((int64_t)H * W * 8 + 15) / 16 * 16; }   // g and d2, rounded up so that the records stay aligned
 
 }  // namespace
 
@@ -257,8 +373,8 @@ extern "C" int msam_edt_squared(const void* mask, int32_t mask_is_int32, int32_t
     }
     hipStream_t s = (hipStream_t)stream;
     int* g = (int*)workspace;
-    if (mask_is_int32) edt_launch<SRC_I32>(mask, nullptr, H, W, g, g + (size_t)H * W, out, s);
-    else edt_launch<SRC_U8>(mask, nullptr, H, W, g, g + (size_t)H * W, out, s);
+    if (mask_is_int32) edt_launch<SRC_I32>(mask, nullptr, H, W, 0, g, g + (size_t)H * W, out, s);
+    else edt_launch<SRC_U8>(mask, nullptr, H, W, 0, g, g + (size_t)H * W, out, s);
     return msam_check_launch("msam_edt_squared");
 }
 
@@ -297,13 +413,63 @@ extern "C" int msam_label_props(const int32_t* labels, int32_t H, int32_t W, con
     if (bad) { msam_set_error("msam_label_props: ids must be positive, distinct and sorted ascending"); return 1; }
     const unsigned nb = (unsigned)((N + 255) / 256);
     hipLaunchKernelGGL(lp_init_kernel, dim3(nb), dim3(256), 0, s, N, area, bbox, (u64*)coord_sum, maxd, first);
-    if (center) edt_launch<SRC_LABELS>(labels, labels, H, W, g, carry, dist, s);
+    if (center) edt_launch<SRC_LABELS>(labels, labels, H, W, 0, g, carry, dist, s);
     const dim3 grid((unsigned)((W + 256 * LP_PER - 1) / (256 * LP_PER)), (unsigned)H);
-    hipLaunchKernelGGL(lp_stats_kernel, grid, dim3(256), 0, s, labels, center ? (const int*)dist : (const int*)nullptr, W, ids, N, index, area,
+    hipLaunchKernelGGL((lp_stats_kernel<false>), grid, dim3(256), 0, s, labels, center ? (const int*)dist : (const int*)nullptr, W, ids, N, index, area,
                        bbox, (u64*)coord_sum, maxd);
     if (center)
-        hipLaunchKernelGGL(lp_center_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, s, (const int*)index, (const int*)dist, (int)npx,
-                           (const int*)maxd, first);
+        hipLaunchKernelGGL((lp_center_kernel<false>), dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, s, (const int*)index, (const int*)dist,
+                           (int)npx, N, (const int*)maxd, first);
     hipLaunchKernelGGL(lp_finish_kernel, dim3(nb), dim3(256), 0, s, N, W, (const int*)area, bbox, (const int*)first, center);
     return msam_check_launch("msam_label_props");
+}
+
+extern "C" int64_t msam_distance_targets_workspace_bytes(int32_t H, int32_t W, int32_t N) {
+    if (!lp_side_ok(H, W) || N < 0) return 0;
+    // g, d2 per pixel; record (16 bytes), coordinate sums (two 64-bit words), area, maximum and first pixel per object; the column pass's carries
+    return dt_pixel_bytes(H, W) + (int64_t)N * 44 + edt_carry_ints(H, W) * 4;
+}
+
+extern "C" int msam_distance_targets(const int32_t* labels, int32_t H, int32_t W, int32_t N, int32_t correct_centers, float fill, float* out,
+                                     int32_t* center, int32_t* dmax2, int32_t* bbox, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!labels || !out || !workspace || (N > 0 && (!center || !dmax2 || !bbox))) { msam_set_error("msam_distance_targets: null pointer"); return 1; }
+    if (!lp_side_ok(H, W)) { msam_set_error("msam_distance_targets: 1 <= H, W <= 32767"); return 1; }
+    if (N < 0) { msam_set_error("msam_distance_targets: N >= 0 objects"); return 1; }
+    if (correct_centers != 0 && correct_centers != 1) { msam_set_error("msam_distance_targets: correct_centers must be 0 or 1"); return 1; }
+    if (((uintptr_t)workspace & 15) != 0) { msam_set_error("msam_distance_targets: the workspace must be 16-byte aligned"); return 1; }
+    if (workspace_bytes < msam_distance_targets_workspace_bytes(H, W, N)) {
+        msam_set_error("msam_distance_targets: the workspace is smaller than msam_distance_targets_workspace_bytes says");
+        return 1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const size_t npx = (size_t)H * W;                                  // <= 32767^2 < 2^30: 32-bit pixel indices
+    int* g = (int*)workspace;
+    int* dist = g + npx;
+    DtObject* table = (DtObject*)((char*)workspace + dt_pixel_bytes(H, W));
+    u64* sums = (u64*)(table + N);
+    int* area = (int*)(sums + 2 * (size_t)N);
+    int* maxd = area + N;
+    int* first = maxd + N;
+    int* carry = first + N;
+    if (N > 0) {
+        const unsigned nb = (unsigned)(((int64_t)N + 255) / 256);
+        hipLaunchKernelGGL(lp_init_kernel, dim3(nb), dim3(256), 0, s, N, area, bbox, sums, maxd, first);
+        edt_launch<SRC_INNER>(labels, labels, H, W, N, g, carry, dist, s);
+        const dim3 grid((unsigned)((W + 256 * LP_PER - 1) / (256 * LP_PER)), (unsigned)H);
+        hipLaunchKernelGGL((lp_stats_kernel<true>), grid, dim3(256), 0, s, labels, (const int*)dist, W, (const int*)nullptr, N, (int*)nullptr, area,
+                           bbox, sums, maxd);
+        hipLaunchKernelGGL((lp_center_kernel<true>), dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, s, labels, (const int*)dist, (int)npx, N,
+                           (const int*)maxd, first);
+        hipLaunchKernelGGL(dt_finish_kernel, dim3(nb), dim3(256), 0, s, labels, W, N, correct_centers, (const int*)area, (const u64*)sums,
+                           (const int*)maxd, (const int*)first, bbox, center, dmax2, table);
+    }
+    const DtObject* tab = N > 0 ? table : nullptr;
+    const bool wide = npx % DT_PER == 0 && (((uintptr_t)labels | (uintptr_t)out) & 15) == 0;
+    if (wide)
+        hipLaunchKernelGGL((dt_write_kernel<DT_PER>), dim3((unsigned)((npx / DT_PER + 255) / 256)), dim3(256), 0, s, labels, (const int*)dist,
+                           (unsigned)npx, (unsigned)W, N, tab, fill, out);
+    else
+        hipLaunchKernelGGL((dt_write_kernel<1>), dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, s, labels, (const int*)dist, (unsigned)npx,
+                           (unsigned)W, N, tab, fill, out);
+    return msam_check_launch("msam_distance_targets");
 }

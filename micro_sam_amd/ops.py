@@ -1173,5 +1173,5 @@ def uncrop_bits(bits: torch.Tensor, crop_box, height: int, width: int) -> torch.
 
 
 from ._matching import label_matching  # noqa: E402,F401  (defined in _matching.py, which uses _home / _need of this module)
-from ._labelprops import LabelProps, edt_squared, label_props  # noqa: E402,F401  (csrc/labelprops.hip; same arrangement)
+from ._labelprops import DistanceTargets, LabelProps, distance_targets, edt_squared, label_props  # noqa: E402,F401  (csrc/labelprops.hip; same arrangement)
 from ._propagate import mask_box_prompts, mask_iou_counts, mask_logits, pack_bits, paint_max  # noqa: E402,F401  (csrc/propagate.hip)

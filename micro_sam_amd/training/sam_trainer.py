@@ -226,6 +226,17 @@ class SamTrainer:
             return 1, 0, False, True
         return 0, 0, True, False            # a single box per object
 
+    # ---- reference :86-120
+    def _get_prompt_and_multimasking_choices_for_val(self, current_iteration):
+        if current_iteration % 4 == 0:      # a single point per object
+            return 1, 0, False, True
+        if current_iteration % 4 == 1:      # a single box per object
+            return 0, 0, True, False
+        n_pos = np.random.randint(1, 5)
+        if current_iteration % 4 == 2:      # a random number of points; (1, 0) is the first case
+            return n_pos, np.random.randint(1 if n_pos == 1 else 0, 5), False, False
+        return n_pos, np.random.randint(0, 5), True, False      # a box and a random number of points
+
     def _compute_iou(self, pred, true, eps=1e-7):
         pred_mask = pred > 0.5
         overlap = pred_mask.logical_and(true).sum(dim=(1, 2, 3))
@@ -344,11 +355,23 @@ class SamTrainer:
             batched_inputs=batched_inputs, y_one_hot=y_one_hot, num_subiter=self.n_sub_iteration, multimask_output=multimask_output)
         return loss, mask_loss, iou_loss, model_iou, y_one_hot
 
+    # ---- reference :427-446
+    def _interactive_val_iteration(self, x, y, val_iteration):
+        n_pos, n_neg, get_boxes, multimask_output = self._get_prompt_and_multimasking_choices_for_val(val_iteration)
+        batched_inputs, sampled_ids = self.convert_inputs(x, y, n_pos, n_neg, get_boxes, self.n_objects_per_batch)
+        batched_inputs, y_one_hot = self._preprocess_batch(batched_inputs, y, sampled_ids)
+        image_embeddings, batched_inputs = self.model.image_embeddings_oft(batched_inputs)
+        batched_outputs = self.model(batched_inputs=batched_inputs, image_embeddings=image_embeddings, multimask_output=multimask_output)
+        loss, mask_loss, iou_regression_loss = self._compute_loss(batched_outputs, y_one_hot)
+        model_iou = torch.mean(torch.stack([m["iou_predictions"] for m in batched_outputs]))
+        return loss, mask_loss, iou_regression_loss, model_iou, y_one_hot, mask_loss      # (the metric is the dice loss of the masks)
+
     # ---- the train step of reference :384-418 (optimizer.zero_grad - forward - backward - step) + gradient all-reduce
-    def train_iteration(self, x, y) -> dict:
+    def _optimization_pass(self, forward: Callable):
+        """One zero - forward - backward - gradient exchange - step sequence over the optimizer's parameters.  ``forward()`` returns a
+        tuple whose first entry is the loss.  -> (that tuple, the bytes all-reduced)."""
         import os
         from ..parallel import collectives_active
-        self.model.train()
         params = [p for g in self.optimizer.param_groups for p in g["params"]]
         overlap = collectives_active() and os.environ.get("MSAM_DP_OVERLAP", "1") != "0"
         if overlap:
@@ -360,10 +383,15 @@ class SamTrainer:
                 self._buckets.remove()
                 self._buckets = None
             self.optimizer.zero_grad()
-        loss, mask_loss, iou_loss, model_iou, _ = self._interactive_train_iteration(x, y)
-        loss.backward()
+        out = forward()
+        out[0].backward()
         reduced = self._buckets.finish() if overlap else all_reduce_gradients(params)
         self.optimizer.step()
+        return out, reduced
+
+    def train_iteration(self, x, y) -> dict:
+        self.model.train()
+        (loss, mask_loss, iou_loss, model_iou, _), reduced = self._optimization_pass(lambda: self._interactive_train_iteration(x, y))
         rec = {"iteration": self._iteration, "loss": float(loss.detach()), "mask_loss": float(mask_loss.detach()),
                "iou_regression_loss": float(iou_loss.detach()), "model_iou": float(model_iou), "allreduce_bytes": reduced}
         self.history.append(rec)
