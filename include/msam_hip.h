@@ -924,6 +924,32 @@ int msam_mask_logits(const uint32_t* bits, int32_t P, int32_t H, int32_t W, floa
 int msam_paint_max(const uint32_t* bits, const int32_t* ids, const uint8_t* keep, int32_t P, int32_t H, int32_t W, int32_t* label,
                    void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * PCA projection of image embeddings for visualization (micro_sam/visualization.py compute_pca, i.e. elf's embedding_pca on sklearn's
+ * PCA; csrc/embedpca.hip).  A call works on U units; a unit is one embedding in its own channel-major layout, float32 [C, N] with
+ * N = H * W positions.  1 <= U <= 65535, 1 <= C <= 256, N >= 1, C * N < 2^31.  The eigen-decomposition of the [C, C] matrix is the
+ * caller's (the host's).  No floating-point atomics; every sum has one fixed order that depends on C and N alone, so two calls agree bit
+ * for bit and a unit's result does not depend on the other units of the batch.  Kernels on `stream`, no synchronisation.
+ * ------------------------------------------------------------------------------------------------- */
+#define MSAM_PCA_MAX_UNITS 65535
+#define MSAM_PCA_MAX_CHANNELS 256
+#define MSAM_PCA_MAX_COMPONENTS 8
+/* x: float32 [U, C, N].  mean: float32 [U, C], the channel means (summed in fp64, rounded once).  gram: double [U, C, C] =
+ * sum_n (x_n - mean)(x_n - mean)^T of the data centred with that fp32 mean (two passes; never sum x x^T - N mean mean^T): fp32 products
+ * and fp32 sums over 64 positions on the f32-input MFMA, every further sum in fp64; the upper triangle of 32 x 32 tiles is computed and
+ * mirrored, so gram is exactly symmetric.  workspace: the caller's, 8-byte aligned (the query returns 0 for a bad shape). */
+int64_t msam_pca_moments_workspace_bytes(int32_t U, int32_t C, int32_t N);
+int msam_pca_moments(const float* x, int32_t U, int32_t C, int32_t N, float* mean, double* gram, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+/* components: float32 [U, K, C], 1 <= K <= 8; mean: float32 [U, C].  out: float32 [U, K, N],
+ * out[u, j, n] = sum_c components[u, j, c] * (x[u, c, n] - mean[u, c]), c ascending, one fused multiply-add per term.
+ * minmax: float32 [U, 2] = the minimum and the maximum of the K * N values of every unit. */
+int msam_pca_project(const float* x, const float* components, const float* mean, int32_t U, int32_t C, int32_t N, int32_t K, float* out,
+                     float* minmax, void* stream);
+/* proj: float32 [U, 3, N], minmax: float32 [U, 2] -> rgb: uint8 [U, N, 3] = trunc((255 * (proj - min)) / (max - min)), the fp32
+ * operations in that order (IEEE division); a unit with max == min gives zeros.  3 * N < 2^31. */
+int msam_pca_to_rgb(const float* proj, const float* minmax, int32_t U, int32_t N, uint8_t* rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

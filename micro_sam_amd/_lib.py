@@ -263,6 +263,10 @@ _PROTOS = {
     "msam_mask_box_prompts": (_i32, [_vp, _i32, _i32, _i32, C.c_double, _i32, _i32, _vp, _vp, _vp]),
     "msam_mask_logits": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "msam_paint_max": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "msam_pca_moments_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "msam_pca_moments": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "msam_pca_project": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "msam_pca_to_rgb": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
 }
 OPTIONAL = set()
 
