@@ -950,6 +950,37 @@ int msam_pca_project(const float* x, const float* components, const float* mean,
  * operations in that order (IEEE division); a unit with max == min gives zeros.  3 * N < 2^31. */
 int msam_pca_to_rgb(const float* proj, const float* minmax, int32_t U, int32_t N, uint8_t* rgb, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * The loss of semantic-segmentation fine-tuning (micro_sam/training/semantic_sam_trainer.py: CustomDiceLoss on a soft-max and a one-hot
+ * target, i.e. torch_em's DiceLoss, plus nn.CrossEntropyLoss; csrc/semloss.hip), fused: two launches forward, one backward.
+ * logits: float32 [B, C, HW] contiguous (every class its own plane per image), 2 <= C <= 32, B * C * HW < 2^31; target: int32 [B, HW]
+ * class ids.  p = softmax_c(logits) per pixel, or p = logits with apply_softmax == 0 (then ce_weight must be 0); t_c = [target == c].
+ *   dice = sum_c (1 - 2 num_c / max(den_c, eps)),  num_c = sum p_c t_c,  den_c = sum p_c^2 + sum t_c, the sums over all B * HW pixels
+ *   ce   = mean over the VALID pixels (0 <= target < C) of logsumexp(logits) - logits[target]
+ *   loss = dice_weight * dice + ce_weight * ce
+ * Two deliberate differences from torch: every id outside [0, C) is ignored by the cross-entropy like torch's ignore_index -100 (torch
+ * raises a device-side assert for the others) - such a pixel still counts in the dice sums with an all-zero one-hot; and without any
+ * valid pixel ce = 0 with a zero gradient (torch: NaN).
+ * stats_out (8-byte aligned, MSAM_SEMLOSS_STATS_WORDS(C) words of 8 bytes): float64 [2 C + 3] = num_c, sum p_c^2, the cross-entropy
+ * sum, dice, ce; then int64 [C + 2] = sum t_c, the number of valid pixels, the number of ignored pixels.  loss_out: one float32.
+ * exp and log are fp32, the soft-max division and every sum are fp64, in one fixed order that depends on the shape and on whether the
+ * four-pixel form runs (HW % 4 == 0 and 16-byte aligned pointers) alone: no floating-point atomics, two calls agree bit for bit.
+ * workspace: the caller's, 8-byte aligned (the query returns 0 for a bad shape).  Kernels on `stream`, no synchronisation.
+ *
+ * backward: dlogits float32 [B, C, HW] = d loss / d logits times the upstream gradient, which is READ ON THE DEVICE from grad_out_ptr
+ * (one float32); `stats` is what the forward call wrote for the same arguments.  With d_c = max(den_c, eps):
+ *   g_c = dice_weight [den_c > eps] (-2 t_c / d_c + 4 num_c p_c / d_c^2)
+ *   dlogits_k = p_k (g_k - sum_c p_c g_c) + ce_weight valid (p_k - t_k) / n_valid      (dlogits = g with apply_softmax == 0) */
+#define MSAM_SEMLOSS_MAX_CLASSES 32
+#define MSAM_SEMLOSS_STATS_WORDS(C) (3 * (C) + 5)
+int64_t msam_semantic_loss_workspace_bytes(int32_t B, int32_t C, int32_t HW);
+int msam_semantic_loss_forward(const float* logits, const int32_t* target, int32_t B, int32_t C, int32_t HW, float dice_weight,
+                               float ce_weight, int32_t apply_softmax, double eps, void* workspace, int64_t workspace_bytes,
+                               float* loss_out, void* stats_out, void* stream);
+int msam_semantic_loss_backward(const float* logits, const int32_t* target, int32_t B, int32_t C, int32_t HW, float dice_weight,
+                                float ce_weight, int32_t apply_softmax, double eps, const void* stats, const float* grad_out_ptr,
+                                float* dlogits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

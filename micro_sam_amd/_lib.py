@@ -267,6 +267,9 @@ _PROTOS = {
     "msam_pca_moments": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     "msam_pca_project": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "msam_pca_to_rgb": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    "msam_semantic_loss_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "msam_semantic_loss_forward": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _i32, C.c_double, _vp, _i64, _vp, _vp, _vp]),
+    "msam_semantic_loss_backward": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _i32, C.c_double, _vp, _vp, _vp, _vp]),
 }
 OPTIONAL = set()
 

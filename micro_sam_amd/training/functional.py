@@ -246,6 +246,38 @@ def relpos_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bias_h: 
     return _RelPosAttention.apply(q, k, v, bias_h, bias_w, scale)
 
 
+class _SemanticLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, dice_weight, ce_weight, softmax):
+        from .._semloss import class_ids
+        lc = logits.contiguous()
+        tgt = class_ids(target)                                        # (converted once; the backward pass reads the same tensor)
+        loss, stats = ops.semantic_loss(lc, tgt, dice_weight, ce_weight, softmax)
+        ctx.save_for_backward(lc, tgt, stats.raw)
+        ctx.weights = (dice_weight, ce_weight, softmax)
+        ctx.mark_non_differentiable(stats.raw)
+        return loss, stats.raw
+
+    @staticmethod
+    def backward(ctx, dloss, _dstats):
+        lc, tgt, raw = ctx.saved_tensors
+        dice_weight, ce_weight, softmax = ctx.weights
+        # the upstream gradient stays on the device: the kernel reads it there
+        up = dloss.to(torch.float32).contiguous()
+        return ops.semantic_loss_backward(lc, tgt, raw, up, dice_weight, ce_weight, softmax), None, None, None, None
+
+
+def semantic_loss(logits: torch.Tensor, target: torch.Tensor, dice_weight: float = 1.0, ce_weight: float = 1.0, softmax: bool = True):
+    """Differentiable ``ops.semantic_loss``: ``dice_weight * dice + ce_weight * ce`` of logits [B, C, H, W] against class ids [B, H, W] or
+    [B, 1, H, W] in two launches forward and one backward -> (loss, ``ops.SemanticLossStats``; the statistics carry no gradient).
+    Logits that are not float32 (bf16 under autocast) are up-cast by autograd's own ``.float()``."""
+    from .._semloss import stats_views
+    if logits.dtype != torch.float32:
+        logits = logits.float()
+    loss, raw = _SemanticLoss.apply(logits, target, float(dice_weight), float(ce_weight), bool(softmax))
+    return loss, stats_views(raw, int(logits.shape[1]))
+
+
 # Which implementation the image encoder's attention takes under autograd (training/encoders.py):
 #   "gemm"   (default) the two products as plain library batched GEMMs on bf16 operands (torch.bmm = rocBLAS / hipBLASLt on MFMA; what
 #            the reference's AMP does), scores + decomposed bias + softmax in fp32 torch operators, backward by autograd.  The score

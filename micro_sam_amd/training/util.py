@@ -1,5 +1,5 @@
-"""``get_trainable_sam_model`` (reference ``micro_sam/training/util.py:77-151``) and ``ConvertToSamInputs`` (``:153-288``: data-loader
-batch -> SAM's batched inputs)."""
+"""``get_trainable_sam_model`` (reference ``micro_sam/training/util.py:77-151``) ``ConvertToSamInputs`` (``:153-288``: data-loader
+batch -> SAM's batched inputs) and ``ConvertToSemanticSamInputs`` (the same for semantic segmentation: no prompts)."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Union
@@ -97,3 +97,11 @@ class ConvertToSamInputs:
             batched_inputs.append(rec)
             batched_ids.append(cell_ids)
         return batched_inputs, batched_ids
+
+
+class ConvertToSemanticSamInputs:
+    """Reference ``ConvertToSemanticSamInputs``: the batch of a data loader as SAM's batched inputs for semantic segmentation - one record
+    per image with the image and its size, and no prompt."""
+
+    def __call__(self, x, y):
+        return [{"image": image, "original_size": image.shape[-2:]} for image in x]
