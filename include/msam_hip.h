@@ -981,6 +981,20 @@ int msam_semantic_loss_backward(const float* logits, const int32_t* target, int3
                                 float ce_weight, int32_t apply_softmax, double eps, const void* stats, const float* grad_out_ptr,
                                 float* dlogits, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * The depth convolution of the 3-d adapter (micro_sam/models/sam_3d_wrapper.py NDBlockWrapper: Conv3d(C, C, kernel_size=(3, 1, 1),
+ * padding="same")) on token-major rows, as an implicit-shift MFMA GEMM (csrc/depthconv.hip): one launch, no im2col copy, no permute.
+ *   out[b, z, t, :] = bias + sum_{j = 0..2} W_j x[b, z + j - 1, t, :]      (a term is dropped when z + j - 1 is outside [0, D))
+ * x: bf16 [B D T, Ci], row (b D + z) T + t, row stride ldx (elements, >= Ci, a multiple of 8); w: bf16 [Co, 3 Ci] contiguous, tap-major
+ * (columns j Ci .. (j + 1) Ci - 1 are tap j, i.e. w[co, j Ci + ci] = conv.weight[co, ci, j, 0, 0]); bias: fp32 [Co] or NULL; out: fp32
+ * [B D T, Co], row stride ldc (>= Co, a multiple of 4).  Ci % 64 == 0, Co % 128 == 0, B, D, T >= 1 otherwise arbitrary (T need not
+ * divide the 128-row tile: a tile may span slices and volumes); x and w below 2^31 bytes each; all pointers 16-byte aligned.  bf16
+ * operands, fp32 accumulation in one fixed order: two calls agree bit for bit; no atomics.  No address outside x is formed.
+ * The input gradient is the same call: dX = conv(dY, W') with W'[ci, j Co + co] = W[co, (2 - j) Ci + ci].
+ * Any other argument: status 1 with the error text set, before any launch.  Kernel on `stream`, no synchronisation. */
+int msam_depth_conv3_bf16(const void* x, int64_t ldx, const void* w, const float* bias, float* out, int64_t ldc, int32_t B, int32_t D,
+                          int32_t T, int32_t Ci, int32_t Co, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

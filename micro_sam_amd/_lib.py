@@ -270,6 +270,7 @@ _PROTOS = {
     "msam_semantic_loss_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "msam_semantic_loss_forward": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _i32, C.c_double, _vp, _i64, _vp, _vp, _vp]),
     "msam_semantic_loss_backward": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _i32, C.c_double, _vp, _vp, _vp, _vp]),
+    "msam_depth_conv3_bf16": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
 }
 OPTIONAL = set()
 

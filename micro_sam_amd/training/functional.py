@@ -140,6 +140,140 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor = None) -> 
     return _Linear.apply(x, weight, bias)
 
 
+# bf16 operands of the depth convolution per parameter and parameter version, as _W16: the tap-major W [Co, 3 Ci] of the forward pass
+# and W' [Ci, 3 Co] (taps reversed, channels transposed) of the input gradient, rows zero-padded to the kernel's 128
+_WCONV16 = {}
+
+
+def _conv_weight16(weight: torch.Tensor):
+    from .._depthconv import tap_major, tap_major_transposed
+
+    def make():
+        w16 = weight.detach().to(torch.bfloat16)
+        co, ci = w16.shape[:2]
+        return (_pad_to(tap_major(w16), (co + 127) // 128 * 128, 3 * ci), _pad_to(tap_major_transposed(w16), (ci + 127) // 128 * 128, 3 * co))
+    if not isinstance(weight, torch.nn.Parameter):
+        return make()
+    key = id(weight)
+    hit = _WCONV16.get(key)
+    stamp = (weight._version, weight.data_ptr(), weight.device.index)
+    if hit is not None and hit[0]() is weight and hit[1] == stamp:
+        return hit[2], hit[3]
+    if len(_WCONV16) > 1024:                 # parameters of discarded models
+        for k in [k for k, v in _WCONV16.items() if v[0]() is None]:
+            del _WCONV16[k]
+    w16, w16t = make()
+    _WCONV16[key] = (weakref.ref(weight), stamp, w16, w16t)
+    return w16, w16t
+
+
+def _mm_nt_cols(at: torch.Tensor, bt: torch.Tensor, ca: int, cb: int, k: int) -> torch.Tensor:
+    """fp32 [Na, Nb] = at[:, ca : ca + k] @ bt[:, cb : cb + k]^T for bf16 ``at`` [Na, M], ``bt`` [Nb, M]: a weight gradient over a RANGE
+    of the rows of the batch.  The product kernel takes row strides, so an aligned range is read in place (split-K as ``_mm_nt``: the
+    slices are added in order, the same bits on every run); any other range goes through ``_mm_nt`` on copies."""
+    na, m = at.shape
+    nb = bt.shape[0]
+    split = 1
+    if k >= 8192:
+        tiles = ((na + 127) // 128) * ((nb + 127) // 128)
+        while tiles < 128 and split * 2 * tiles <= 512 and k // (split * 2) >= 1024 and k % (128 * split) == 0:
+            split *= 2
+    if (k % (64 * split) or nb % 128 or m % 8 or ca % 8 or cb % 8 or not at.is_contiguous() or not bt.is_contiguous()
+            or at.data_ptr() % 16 or bt.data_ptr() % 16):
+        return _mm_nt(at[:, ca:ca + k], bt[:, cb:cb + k])
+    out = torch.empty((na, nb), dtype=torch.float32, device=at.device)
+    p = _lib.GemmParams()
+    p.A, p.lda, p.W, p.ldw, p.M, p.N, p.K = at.data_ptr() + 2 * ca, m, bt.data_ptr() + 2 * cb, m, na, nb, k
+    p.out, p.out_dtype, p.ldc = out.data_ptr(), _lib.F32, nb
+    p.split_k = split if split > 1 else 0
+    _lib.check(_lib.load().msam_gemm_bf16(C.byref(p), _lib.stream_ptr()), "msam_gemm_bf16(rows)")
+    return out
+
+
+class _DepthConv3(torch.autograd.Function):
+    """The 3-d adapter's ``Conv3d(Ci, Co, (3, 1, 1), padding="same")`` on token-major rows (csrc/depthconv.hip).  Forward: one
+    ``ops.cast_transpose`` of x (its bf16 copy, and X^T if the weight trains), then the kernel.  Backward: one ``ops.cast_transpose`` of
+    dY (bf16 copy, dY^T, the column sums = the bias gradient), dX by the SAME kernel on W' (taps reversed, channels transposed), and
+    dW per tap = dY^T shift_j(X) on the split-K product kernel over the rows whose tap lies inside the volume: the centre tap over all
+    rows at once, an outer tap over D - 1 slices of each volume, the volumes added in index order - the same bits on every run."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, depth):
+        shape = x.shape
+        ci, co = int(weight.shape[1]), int(weight.shape[0])
+        x2 = x.reshape(-1, ci)
+        m = x2.shape[0]
+        t = int(shape[1]) * int(shape[2])
+        vols = int(shape[0]) // depth
+        need_dw = weight.requires_grad
+        if _fusable(x2):
+            a16, a16t, _ = ops.cast_transpose(x2, True, need_dw, False)
+        else:
+            a16 = x2.to(torch.bfloat16).contiguous()
+            a16t = a16.t().contiguous() if need_dw else None
+        w16, w16t = _conv_weight16(weight)
+        b = None if bias is None else bias.detach().float().contiguous()
+        if b is not None and w16.shape[0] != co:
+            b = torch.nn.functional.pad(b, (0, w16.shape[0] - co))
+        y = ops.depth_conv3(a16, w16, b, vols, depth, t)
+        if w16.shape[0] != co:
+            y = y[:, :co]
+        ctx.save_for_backward(a16t if need_dw else None, w16t)
+        ctx.has_bias = bias is not None
+        ctx.geom = (shape, vols, depth, t, m, ci, co)
+        return y.reshape(*shape[:-1], co)
+
+    @staticmethod
+    def backward(ctx, dy):
+        a16t, w16t = ctx.saved_tensors
+        shape, vols, depth, t, m, ci, co = ctx.geom
+        dy2 = dy.reshape(m, co)
+        want_dx = ctx.needs_input_grad[0]
+        want_dw = ctx.needs_input_grad[1] and a16t is not None
+        want_db = ctx.has_bias and ctx.needs_input_grad[2]
+        if _fusable(dy2):
+            dy16, dy16t, db = ops.cast_transpose(dy2, want_dx, want_dw, want_db)
+        else:
+            dy2 = dy2.contiguous()
+            dy16 = dy2.to(torch.bfloat16)
+            dy16t = dy16.t().contiguous() if want_dw else None
+            db = dy2.float().sum(dim=0) if want_db else None
+        dx = dw = None
+        if want_dx:
+            dx = ops.depth_conv3(dy16, w16t, None, vols, depth, t)                   # dX = conv(dY, W')
+            if w16t.shape[0] != ci:
+                dx = dx[:, :ci]
+            dx = dx.reshape(shape)
+        if want_dw:
+            taps = []
+            for j in range(3):
+                if j == 1:
+                    taps.append(_mm_nt_cols(dy16t, a16t, 0, 0, m))
+                    continue
+                acc = None
+                span = (depth - 1) * t                                               # rows of a volume whose tap j is inside it
+                for v in range(vols if span > 0 else 0):
+                    r0 = v * depth * t
+                    # tap 0 reads the slice before (dY rows from the second slice on), tap 2 the slice after
+                    part = _mm_nt_cols(dy16t, a16t, r0 + t, r0, span) if j == 0 else _mm_nt_cols(dy16t, a16t, r0, r0 + t, span)
+                    acc = part if acc is None else acc + part
+                taps.append(acc if acc is not None else torch.zeros((co, ci), dtype=torch.float32, device=dy.device))
+            dw = torch.stack(taps, dim=2).reshape(co, ci, 3, 1, 1)
+        return dx, dw, db if want_db else None, None
+
+
+def depth_conv3(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, depth: int) -> torch.Tensor:
+    """``nn.Conv3d(Ci, Co, (3, 1, 1), padding="same")`` along the slices of token-major volumes: x fp32 [B * depth, H, W, Ci] (the
+    ``depth`` slices of a volume are consecutive), weight [Co, Ci, 3, 1, 1] (the reference's parameter shape), bias [Co] or None ->
+    fp32 [B * depth, H, W, Co].  bf16 operands, fp32 accumulation in both directions; Ci and Co are multiples of 64."""
+    if x.dim() != 4 or weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 1, 1) or x.shape[-1] != weight.shape[1]:
+        raise ValueError(f"depth_conv3: x must be [B * depth, H, W, Ci] and weight [Co, Ci, 3, 1, 1], got {tuple(x.shape)} and "
+                         f"{tuple(weight.shape)}")
+    if isinstance(depth, bool) or not isinstance(depth, int) or depth < 1 or x.shape[0] % depth != 0:
+        raise ValueError(f"depth_conv3: depth = {depth!r} must be a positive int that divides the {x.shape[0]} slices")
+    return _DepthConv3.apply(x, weight, bias, depth)
+
+
 class _LayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps):

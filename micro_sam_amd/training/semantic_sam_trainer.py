@@ -26,10 +26,23 @@ from . import functional as HF
 from .sam_trainer import SamTrainer
 
 
+def _fold_depth(pred: torch.Tensor, target: torch.Tensor):
+    """Volumes (``models.sam_3d_wrapper.Sam3DWrapper``): prediction [B, C, D, H, W] with target [B, 1, D, H, W] or [B, D, H, W] ->
+    [B, C, D H, W] and [B, D H, W].  Exact for this loss: the dice sums and the cross-entropy mean run over batch and space per class,
+    so it does not matter which spatial axis a pixel lies on.  Anything else passes through."""
+    if pred.dim() != 5:
+        return pred, target
+    b, c, d, h, w = pred.shape
+    if tuple(target.shape) not in ((b, 1, d, h, w), (b, d, h, w)):
+        raise ValueError(f"the target of a prediction {tuple(pred.shape)} must be {(b, 1, d, h, w)} or {(b, d, h, w)}, got {tuple(target.shape)}")
+    return pred.reshape(b, c, d * h, w), target.reshape(b, d * h, w)
+
+
 class CustomDiceLoss(nn.Module):
     """The reference's ``CustomDiceLoss``: dice over one-hot labels.  prediction [B, num_classes, H, W], target [B, 1, H, W] (or
     [B, H, W]) class ids -> torch_em ``DiceLoss()`` of the (soft-max of the) prediction against the one-hot target, summed over the
-    classes.  One fused device call with ``ce_weight=0``."""
+    classes.  One fused device call with ``ce_weight=0``.  Volumes, prediction [B, num_classes, D, H, W] with target [B, 1, D, H, W] or
+    [B, D, H, W], are folded to images first (``_fold_depth``)."""
 
     def __init__(self, num_classes: int, softmax: bool = True) -> None:
         super().__init__()
@@ -37,6 +50,7 @@ class CustomDiceLoss(nn.Module):
         self.softmax = bool(softmax)
 
     def forward(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        pred, target = _fold_depth(pred, target)
         if pred.dim() != 4 or pred.shape[1] != self.num_classes:
             raise ValueError(f"CustomDiceLoss: the prediction must be [B, {self.num_classes}, H, W], got {tuple(pred.shape)}")
         return HF.semantic_loss(pred, target, dice_weight=1.0, ce_weight=0.0, softmax=self.softmax)[0]
@@ -76,7 +90,9 @@ class SemanticSamTrainer(SamTrainer):
     # ---- reference :78-93
     def _compute_loss(self, y, masks):
         """The combined (weighted) dice and cross-entropy loss between the prediction [B, num_classes, H, W] and the target
-        [B, 1, H, W] (class ids)."""
+        [B, 1, H, W] (class ids); for a volumetric model [B, num_classes, D, H, W] and [B, 1, D, H, W] or [B, D, H, W], folded to
+        images first (``_fold_depth``)."""
+        masks, y = _fold_depth(masks, y)
         if masks.dim() != 4 or masks.shape[1] != self.num_classes:
             raise ValueError(f"SemanticSamTrainer: the model gives {masks.shape[1] if masks.dim() == 4 else tuple(masks.shape)} channels for "
                              f"num_classes = {self.num_classes} (TrainableSAM with multimask_output=True gives 3)")
