@@ -209,6 +209,20 @@ int msam_i2t0_t2i_fused_v2(const void* tables, const void* tables2, const void* 
                            int64_t workspace_bytes, void* stream);
 int msam_i2t01_fused(const void* tables, const void* operands0, const float* ln0_w, const float* ln0_b, const void* operands1,
                      const float* ln1_w, const float* ln1_b, float ln_eps, int32_t P, int32_t Nt, void* out, void* stream);
+/* Hand-over between the two chained kernels.  Both compute the same layer-0 block for every (prompt, 16-token tile);
+ * msam_i2t0_t2i_fused_v2_handover also stores the block's two small results per tile into `handover`
+ * (>= msam_chain_handover_bytes(P) = P * 256 * 2176 B): [P][256 tiles][pk0: 64 lanes x 16 B][pk1: 64 lanes x 16 B][16 tokens x
+ * (rstd, -mean rstd) fp32] - the packed softmax probabilities as they enter the second product, and the LayerNorm statistics.
+ * msam_i2t01_fused_handover reads them and runs neither the layer-0 scores and softmax nor the sums of the statistics; the rest of
+ * its arithmetic is that of msam_i2t01_fused.  Same bits as the pair without hand-over (out of both kernels).  The caller
+ * orders the two launches (same stream, or an event) and keeps operands0 / tables / Nt the same for both. */
+int64_t msam_chain_handover_bytes(int32_t P);
+int msam_i2t0_t2i_fused_v2_handover(const void* tables, const void* tables2, const void* operands0, const void* mf, const float* ln0_w,
+                                    float ln_eps, const void* qtok, int32_t P, int32_t Nt, const void* wk, void* out, void* workspace,
+                                    int64_t workspace_bytes, void* handover, void* stream);
+int msam_i2t01_fused_handover(const void* tables, const void* operands0, const float* ln0_w, const float* ln0_b, const void* operands1,
+                              const float* ln1_w, const float* ln1_b, float ln_eps, int32_t P, int32_t Nt, const void* handover,
+                              void* out, void* stream);
 
 /* Output up-scaling + hyper-network product of the mask decoder in one pass over the image-token stream (reference:
  * segment_anything/modeling/mask_decoder.py MaskDecoder.predict_masks: output_upscaling = ConvTranspose2d(256,64,2,2),
@@ -245,7 +259,10 @@ int msam_fold_attn_set_dma(int32_t on);
 /* named integer tuning knobs of the decoder stream kernels (A/B experiments, tests): "i2t_variant" (1 = token-owner kernel,
  * default; 0 = 4-wave tile kernel), "i2t_wg_per_cu", "dec_chain" (1 = the decoder takes the chained forms above when the
  * prompts share one source, Nt <= 8 and P >= "dec_chain_min_p"; default 1 / 128), "chain_variant" (builds of the chained
- * kernels: 9 = default, second attention form; 6 = first form; csrc/decfold_tok.hip), "up_gelu16" (1 = the up-scaling's GELUs in packed fp16 arithmetic, default in the fp16 decoder build;
+ * kernels: 9 = default, second attention form; 6 = first form; csrc/decfold_tok.hip), "chain_handover" (1 = default: with
+ * "chain_variant" 9 the decoder passes the layer-0 probabilities and LayerNorm statistics from the attention kernel to the stream
+ * kernel, msam_chain_handover_bytes of its workspace; 0 = the launches without it), "chain_handover_ring" (ring depth of the
+ * hand-over stream kernel, 3 = default or 2), "up_gelu16" (1 = the up-scaling's GELUs in packed fp16 arithmetic, default in the fp16 decoder build;
  * 0 = packed fp32).  Returns 0, 1 for an unknown key. */
 int msam_tune_set(const char* key, int32_t value);
 /* debug hook: phase timing of the folded image->token kernel (see csrc/decfold.hip, tools/i2t_timing.py) */

@@ -180,6 +180,9 @@ _PROTOS = {
     "msam_i2t_fold_operands_values": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "msam_i2t0_t2i_v2_workspace_bytes": (_i64, [_i32]),
     "msam_i2t0_t2i_fused_v2": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "msam_chain_handover_bytes": (_i64, [_i32]),
+    "msam_i2t0_t2i_fused_v2_handover": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "msam_i2t01_fused_handover": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _vp, _vp, _vp]),
     "msam_chain_tables_bytes": (_i64, []),
     "msam_chain_prepare_tables": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "msam_upscale_fused_layout": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),

@@ -782,12 +782,16 @@ extern "C" int msam_fold_attn_set_dma(int32_t on) { g_fold_attn_dma = on; return
 //   "i2t_wg_per_cu"   workgroups per CU of the token-owner kernel's persistent grid (default 2)
 //   "dec_chain"       1 = decoder_run chains layer 0 into layer 1 on a shared source (decfold_tok.hip), 0 = one kernel per stage
 //   "dec_chain_min_p" smallest number of prompts for which it does (default 128)
+//   "chain_handover"  1 (default) = with "chain_variant" 9 the attention kernel hands the layer-0 probabilities and LayerNorm statistics
+//                     to the stream kernel through the decoder workspace; 0 = the launches without the hand-over
+//   "chain_handover_ring" ring depth of the hand-over stream kernel: 3 (default) or 2
 extern int g_tune_i2t_wg_per_cu, g_tune_chain_variant, g_tune_chain_tmask, g_tune_up_gelu16, g_tune_up_ln_two_pass, g_tune_up_centred;
 void msam_gemm_set_dbg(int v);
 void msam_gemm_set_gw(int delay, int cls);
 void msam_gemm_set_g3(int delay);
 void msam_gemm_set_g3_epi(int v);
 extern int g_tune_tok_fuse;
+extern int g_tune_chain_handover, g_tune_chain_handover_ring;
 extern int g_tune_mlp_split_fused;
 extern int g_tune_sgemm_bufs, g_tune_srel_mfma, g_tune_sgemm_small_below, g_tune_si2t_dbg, g_tune_si2t_late_us, g_tune_sattn_allh;
 int g_tune_dec_chain = 1, g_tune_dec_chain_min_p = 128;
@@ -798,6 +802,8 @@ extern "C" int msam_tune_set(const char* key, int32_t value) {
     else if (k == "dec_chain") g_tune_dec_chain = value;
     else if (k == "chain_variant") g_tune_chain_variant = value;
     else if (k == "chain_tmask") g_tune_chain_tmask = value;
+    else if (k == "chain_handover") g_tune_chain_handover = value;
+    else if (k == "chain_handover_ring") g_tune_chain_handover_ring = value;
     else if (k == "up_gelu16") g_tune_up_gelu16 = value;
     else if (k == "up_ln_two_pass") g_tune_up_ln_two_pass = value;
     else if (k == "up_centred") g_tune_up_centred = value;

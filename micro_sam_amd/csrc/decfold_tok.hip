@@ -34,6 +34,9 @@ int g_tune_chain_tmask = 255;        // experiment: tile index mask of the SHARE
 int g_tune_chain_variant = 9;        // chained kernels: 9 (default) = second form of the attention (V projection before the LayerNorm) + tile loads
                                      // one phase ahead; 6 = first form, loads one phase ahead; 0 = first form, 4-fragment groups; 1 / 2 = 4 waves
                                      // (one per SIMD), rings of 8 / 16; 3 = 8 waves on the ring code; 4 / 5 / 7 / 8 = ring depth 3 / compact accumulators
+int g_tune_chain_handover = 1;       // variant 9 in the decoder: 1 (default) = the attention kernel hands its layer-0 softmax probabilities and LayerNorm
+                                     // statistics to the stream kernel (msam_chain_handover_bytes); 0 = the stream kernel computes them again
+int g_tune_chain_handover_ring = 3;  // ring depth of the hand-over stream kernel: 3 (default) or 2 (profiles/r12_chain_handover.md)
 
 namespace {
 
@@ -338,7 +341,16 @@ struct ChainArgs {
     const float* ln1_w; const float* ln1_b;
     float eps; int Nt, P;
     u16* out;                            // d16 [P] blocked [256 tiles][8][64][8]  keys2
+    const unsigned char* hand;           // [P][256 tiles][HAND_TILE] layer-0 probabilities and statistics (i2t01_hand_kernel only)
 };
+
+// HAND-OVER of the layer-0 block's small results from the attention kernel (i2t0_t2i_v2_kernel, which holds them in registers) to
+// the stream kernel (i2t01_hand_kernel), which then skips the layer-0 scores, softmax and LayerNorm sums.  Per (prompt, 16-token tile):
+//     [pk[0]: 64 lanes x 16 B][pk[1]: 64 lanes x 16 B][16 tokens x (rstd, -mean rstd) fp32]
+// pk = the packed probabilities exactly as the block feeds them to its second product (lane-major: one store / load = 1 KiB
+// contiguous per wave); the statistics are written by the lanes l < 16 (token l) and read by every lane for its token l & 15.
+constexpr int HAND_STAT = 2 * FRAG, HAND_TILE = HAND_STAT + 16 * 8;        // 2176 B
+constexpr long HAND_PROMPT = 256L * HAND_TILE;
 
 constexpr int NTHR8 = 512;
 // LDS images of the chained kernels (byte offsets)
@@ -600,7 +612,7 @@ __global__ __launch_bounds__(NTHR8, 2) void i2t0_t2i_kernel(FuseArgs a) {
 // the next product), and across the tile boundary (the operands do not change within a prompt).  G = 4 is the scheme of the
 // kernels above; G = 8 / 16 keep 8 / 16 ds_read_b128 per wave in flight (the LDS latency under load is ~3 of the 16-cycle
 // MFMAs per batch of 4), which needs the registers of a 4-wave workgroup with ONE wave per SIMD (NW = 4: 512 VGPRs per wave).
-template <int G, int D = 2> struct Ring { uint4 buf[D][G]; };     // D slots: batches k .. k + D - 2 in flight behind batch k
+template <int G, int D = 2> struct Ring { uint4 buf[D][G]; int hi; };     // D slots: batches k .. k + D - 2 in flight behind batch k; hi: Off::SPLIT
 
 // ABL (ablation builds for tools/chain_ablation.py only; results are then meaningless): bit 0 no layer-0 score MFMAs, 1 no
 // layer-0 V'^T MFMAs, 2 no LayerNorm, 3 no attention score MFMAs, 4 no V-projection MFMAs, 5 no LDS operand reads, 6 no softmax exps
@@ -608,7 +620,14 @@ template <int G, class Off, int ABL = 0>
 MSAM_DEVINL void ring_fill(Ring<G, Off::D>& r, const unsigned char* L, int batch) {
     if (ABL & 32) return;
 #pragma unroll
-    for (int j = 0; j < G; ++j) r.buf[batch % Off::D][j] = *(const uint4*)(L + Off::off((batch * G + j) % Off::N));
+    for (int j = 0; j < G; ++j) {
+        const int o = Off::off((batch * G + j) % Off::N);
+        // SPLIT: a ds_read's immediate offset has 16 bits.  Beyond 64 KiB the compiler keeps one address REGISTER per fragment (all loop
+        // invariant: ~50 registers of an image of 104 KiB); with ring.hi = 65536 in a register it cannot see through, those fragments are
+        // immediates again, on the one second base L + hi
+        if (Off::SPLIT && o >= 65536) r.buf[batch % Off::D][j] = *(const uint4*)(L + r.hi + (o - 65536));
+        else r.buf[batch % Off::D][j] = *(const uint4*)(L + o);
+    }
 }
 // at fragment n_ of the tile's stream: when it opens a batch, issue the reads of the next one
 #define RING_STEP(n_) do { if ((n_) % G == 0) { TK_FENCE(); ring_fill<G, Off, ABL>(ring, L, (n_) / G + Off::D - 1); TK_FENCE(); } } while (0)
@@ -768,6 +787,7 @@ MSAM_DEVINL void t2i_block_r(Ring<G, Off::D>& ring, const unsigned char* L, cons
 // fragment streams (byte offsets in the kernels' LDS images); N = fragments per tile incl. padding reads: a multiple of 2 G
 template <int G, int D_ = 2> struct ChainOff {               // i2t01: [KT0 8][VF0 32][KF1 / KT1 40][VF1 32]
     static constexpr int D = D_, USED = 112, N = ((USED + D * G - 1) / (D * G)) * (D * G);
+    static constexpr bool SPLIT = false;
     static __device__ constexpr int off(int n) {
         if (n < 8) return C_KT0 + ((n % 4) * 2 + n / 4) * FRAG;
         if (n < 40) return C_VF0 + (n - 8) * FRAG;
@@ -778,6 +798,7 @@ template <int G, int D_ = 2> struct ChainOff {               // i2t01: [KT0 8][V
 };
 template <int G, int D_ = 2> struct FuseOff {                // i2t0_t2i: [KT0 8][VF0 32][QF / QD 36][WV 64]
     static constexpr int D = D_, USED = 140, N = ((USED + D * G - 1) / (D * G)) * (D * G);
+    static constexpr bool SPLIT = false;
     static __device__ constexpr int off(int n) {
         if (n < 8) return F_KT0 + ((n % 4) * 2 + n / 4) * FRAG;
         if (n < 40) return F_VF0 + (n - 8) * FRAG;
@@ -838,6 +859,116 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 1 : 2) void i2t01_ring_kernel(Ch
             uint4 y1[8], y2[8];
             i2t_block_r<G, Off, 0, false>(ring, L, gp0, a.eps, b, qi, wc, y1, [&]() { if (LATE) CH_LOAD1(tile); else CH_LOAD0(nx); });
             i2t_block_r<G, Off, 40, true>(ring, L, gp1, a.eps, y1, tb, wc, y2, [&]() { if (LATE) CH_LOAD0(nx); else CH_LOAD1(nx); });
+#pragma unroll
+            for (int i = Off::USED; i < Off::N; ++i) RING_STEP(i);
+#pragma unroll
+            for (int c2 = 0; c2 < 8; ++c2) buf_store16(y2[c2], ro, voff, tile * (16 * C * 2) + c2 * FRAG);
+        }
+#undef CH_LOAD0
+#undef CH_LOAD1
+    }
+}
+
+// ---- i2t01 with the layer-0 probabilities and LayerNorm statistics handed over by the attention kernel (HAND_TILE above).
+// The layer-0 half keeps the residual MFMAs, the 32 V'^T MFMAs (same operands, same order: the accumulators are bit for bit
+// those of i2t_block_r), the normalise + affine and the pack; it has no score MFMAs, no softmax, no sums and no q0 tile.
+template <int G, int D_ = 2> struct ChainOffH {              // [VF0 32][KF1 / KT1 40][VF1 32]
+    static constexpr int D = D_, USED = 104, N = ((USED + D * G - 1) / (D * G)) * (D * G);
+    static constexpr bool SPLIT = true;                      // see ring_fill
+    static __device__ constexpr int off(int n) {
+        if (n < 32) return C_VF0 + n * FRAG;
+        if (n < 72) { const int i = n - 32, g = i / 4, m = i % 4; return g < 8 ? C_KF1 + (m * 8 + g) * FRAG : C_KT1 + (m * 2 + (g - 8)) * FRAG; }
+        if (n < 104) return C_VF1 + (n - 72) * FRAG;
+        return C_VF0;                                        // padding
+    }
+};
+
+template <int G, class Off, int BASE, class F>
+MSAM_DEVINL void i2t_block_h(Ring<G, Off::D>& ring, const unsigned char* L, const float* gp, const uint4* b, const uint4* pk,
+                             const uint4& stat2, const WaveConst& wc, uint4* y, F&& consumed) {
+    constexpr int ABL = 0;
+    f32x4_t o[16];
+#pragma unroll
+    for (int ct = 0; ct < 16; ++ct) o[ct] = mfma16d(wc.sel[ct & 1], b[ct >> 1], f32x4_t{0.f, 0.f, 0.f, 0.f});
+    consumed();
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        const int n = BASE + i;
+        RING_STEP(n);
+        o[i % 16] = mfma16d(RING_AT(n), pk[i / 16], o[i % 16]);
+    }
+    const bool odd = (__lane_id() & 1) != 0;                 // stat2 = (rstd, -mean rstd) of tokens 2 (fr >> 1) and 2 (fr >> 1) + 1
+    const float rstd = __uint_as_float(odd ? stat2.z : stat2.x), nmr = __uint_as_float(odd ? stat2.w : stat2.y);
+#pragma unroll
+    for (int c2 = 0; c2 < 8; ++c2) {
+        const float4 g0 = *(const float4*)(gp + c2 * 32), g1 = *(const float4*)(gp + c2 * 32 + 4);
+        const float4 h0 = *(const float4*)(gp + C + c2 * 32), h1 = *(const float4*)(gp + C + c2 * 32 + 4);
+        const f32x4_t x0 = o[2 * c2], x1 = o[2 * c2 + 1];
+        y[c2].x = pack2d(fmaf(fmaf(x0[0], rstd, nmr), g0.x, h0.x), fmaf(fmaf(x0[1], rstd, nmr), g0.y, h0.y));
+        y[c2].y = pack2d(fmaf(fmaf(x0[2], rstd, nmr), g0.z, h0.z), fmaf(fmaf(x0[3], rstd, nmr), g0.w, h0.w));
+        y[c2].z = pack2d(fmaf(fmaf(x1[0], rstd, nmr), g1.x, h1.x), fmaf(fmaf(x1[1], rstd, nmr), g1.y, h1.y));
+        y[c2].w = pack2d(fmaf(fmaf(x1[2], rstd, nmr), g1.z, h1.z), fmaf(fmaf(x1[3], rstd, nmr), g1.w, h1.w));
+    }
+}
+
+// Tile loads one phase ahead (LATE of i2t01_ring_kernel): the table tile of layer 1 during the layer-0 half of the SAME tile; the
+// source tile, the probabilities and the statistics of the next tile during the second half of layer 1.
+template <int G, int D>
+__global__ __launch_bounds__(NTHR8, 2) void i2t01_hand_kernel(ChainArgs a) {
+    typedef ChainOffH<G, D> Off;
+    constexpr int ABL = 0;
+    constexpr int NW = 8, NT = 256 / NW;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[C_LDS];
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), fr = lane & 15, fg = lane >> 4;
+    float* prm = (float*)(lds + C_PRM);                      // ln0_w, ln0_b, ln1_w, ln1_b
+    for (int i = tid; i < 4 * C; i += NTHR8) prm[i] = i < C ? a.ln0_w[i] : i < 2 * C ? a.ln0_b[i - C] : i < 3 * C ? a.ln1_w[i - 2 * C] : a.ln1_b[i - 3 * C];
+    const WaveConst wc = wave_const(fr, fg, a.Nt);
+    const int voff = lane * 16;
+    const int soff = (fr >> 1) * 16;                         // statistics of tokens 2 (fr >> 1), + 1: one aligned 16-byte load, this lane's half picked at the use
+    const rsrc_t rsrc = make_rsrc(a.src, T * C * 2), rtab = make_rsrc(a.tabq1, T * CI * 2);
+    const unsigned char* const L = lds + lane * 16;
+    const float* const gp0 = prm + fg * 8;
+    const float* const gp1 = prm + 2 * C + fg * 8;
+    Ring<G, D> ring;
+    ring.hi = 65536;
+    asm volatile("" : "+v"(ring.hi));
+    for (int p = (int)blockIdx.x; p < a.P; p += (int)gridDim.x) {
+        __syncthreads();
+        {
+            int ptid = w * 64 + (voff >> 4);                 // = tid, rebuilt from what the tile loop holds anyway; opaque, so that neither tid nor the
+            asm volatile("" : "+v"(ptid));                   // copy addresses are held (and spilled) across the tile loop
+            const uint4* s0 = (const uint4*)(a.oper0 + (long)p * (OPER_BYTES / 2));
+            const uint4* s1 = (const uint4*)(a.oper1 + (long)p * (OPER_BYTES / 2));
+            for (int i = ptid; i < VF_BYTES / 16; i += NTHR8) ((uint4*)(lds + C_VF0))[i] = s0[VF_OFF / 16 + i];
+#pragma unroll 3
+            for (int i = ptid; i < OPER_BYTES / 16; i += NTHR8) ((uint4*)(lds + C_KT1))[i] = s1[i];
+        }
+        __syncthreads();
+        const rsrc_t ro = make_rsrc(a.out + (long)p * T * C, T * C * 2);
+        const rsrc_t rh = make_rsrc(a.hand + (long)p * HAND_PROMPT, (uint32_t)HAND_PROMPT);
+        uint4 b[8], pk[2], tb[4], st;
+#define CH_LOAD0(tile_)                                                                            \
+        do {                                                                                       \
+            const int so_ = (tile_) * (16 * C * 2), ho_ = (tile_) * HAND_TILE;                     \
+            _Pragma("unroll") for (int s_ = 0; s_ < 8; ++s_) b[s_] = buf_load16(rsrc, voff, so_ + s_ * FRAG);    \
+            pk[0] = buf_load16(rh, voff, ho_); pk[1] = buf_load16(rh, voff, ho_ + FRAG);           \
+            st = buf_load16(rh, soff, ho_ + HAND_STAT);                                            \
+        } while (0)
+#define CH_LOAD1(tile_)                                                                            \
+        do {                                                                                       \
+            const int to_ = (tile_) * (16 * CI * 2);                                               \
+            _Pragma("unroll") for (int s_ = 0; s_ < 4; ++s_) tb[s_] = buf_load16(rtab, voff, to_ + s_ * FRAG);   \
+        } while (0)
+        CH_LOAD0(w);
+        wait_vmem_all();
+#pragma unroll
+        for (int k = 0; k + 1 < D; ++k) ring_fill<G, Off>(ring, L, k);
+        for (int n = 0; n < NT; ++n) {
+            asm volatile("" ::: "memory");
+            const int tile = w + NW * n, nx = w + NW * (n + 1 < NT ? n + 1 : NT - 1);
+            uint4 y1[8], y2[8];
+            i2t_block_h<G, Off, 0>(ring, L, gp0, b, pk, st, wc, y1, [&]() { CH_LOAD1(tile); });
+            i2t_block_r<G, Off, 32, true>(ring, L, gp1, a.eps, y1, tb, wc, y2, [&]() { CH_LOAD0(nx); });
 #pragma unroll
             for (int i = Off::USED; i < Off::N; ++i) RING_STEP(i);
 #pragma unroll
@@ -981,8 +1112,9 @@ constexpr long T2_WOWV = 0, T2_CD = 128 * 128 * 4, T2_GD = T2_CD + 512, T2_BWV =
                T2_TABV = T2_KB + 512, T2_WVG = T2_TABV + (long)T * CI * 2 /* gamma Wv d16 [128][256] */,
                T2_TABV_RM = T2_WVG + (long)CI * C * 2 /* row-major product before the relayout */, T2_BYTES = T2_TABV_RM + (long)T * CI * 2;
 
-template <int G, int D_ = 2> struct FuseOff2 {               // [KT0 8][VF0 32][QF / QD 36][MF 16]
+template <int G, int D_ = 2, bool SPLIT_ = false> struct FuseOff2 {               // [KT0 8][VF0 32][QF / QD 36][MF 16]
     static constexpr int D = D_, USED = 92, N = ((USED + D * G - 1) / (D * G)) * (D * G);
+    static constexpr bool SPLIT = SPLIT_;
     static __device__ constexpr int off(int n) {
         if (n < 8) return AttnOff2::KT0 + ((n % 4) * 2 + n / 4) * FRAG;
         if (n < 40) return AttnOff2::VF0 + (n - 8) * FRAG;
@@ -1000,6 +1132,7 @@ struct FuseArgs2 {
     const u16* mf;                       // per prompt M fragments
     float eps; int Nt, P;
     u16* out;
+    unsigned char* hand;                 // null, or [P][256 tiles][HAND_TILE]: the layer-0 probabilities and statistics of every tile (HAND build)
 };
 
 // colc / gd: this lane's column constants in LDS (float index 16 ct + (l & 15) / 16 dv + (l & 15), read where they are used)
@@ -1071,9 +1204,10 @@ MSAM_DEVINL void t2i_block_v2(Ring<G, Off::D>& ring, const unsigned char* L, con
     }
 }
 
-template <int NW, int G>
+template <int NW, int G, int HD = 0>                         // HD: 0 = no hand-over; else the hand-over build, with ring depth HD
 __global__ __launch_bounds__(64 * NW, 2) void i2t0_t2i_v2_kernel(FuseArgs2 a) {
-    typedef FuseOff2<G, 2> Off;
+    constexpr bool HAND = HD != 0;
+    typedef FuseOff2<G, HAND ? HD : 2, HAND> Off;            // HAND: second LDS base (ring_fill)
     constexpr int ABL = 0;
     constexpr int NTH = 64 * NW, NT = 256 / NW;
     __shared__ __attribute__((aligned(16))) unsigned char lds[AttnOff2::LDS > 8 * MERGE_FLOATS * 4 ? AttnOff2::LDS : 8 * MERGE_FLOATS * 4];
@@ -1086,18 +1220,24 @@ __global__ __launch_bounds__(64 * NW, 2) void i2t0_t2i_v2_kernel(FuseArgs2 a) {
     if (tid < 128) ((float*)(lds + AttnOff2::GDT))[tid] = a.gd[tid];
     const float* const colc = (const float*)(lds + AttnOff2::COLC) + fr;
     const float* const gdl = (const float*)(lds + AttnOff2::GDT) + fr;
-    Ring<G, 2> ring;
+    Ring<G, Off::D> ring;
+    ring.hi = 65536;
+    if (HAND) asm volatile("" : "+v"(ring.hi));
     for (int p = (int)blockIdx.x; p < a.P; p += (int)gridDim.x) {
         __syncthreads();
+        // HAND: the per-lane addresses of the per-prompt code (operand copies here, merge below) are rebuilt for every prompt from
+        // opaque copies of tid / lane; held across the tile loop they are spilled around it (the stores take the registers they had)
+        int ptid = tid, plane = lane;
+        if (HAND) asm volatile("" : "+v"(ptid), "+v"(plane));
         {
             const uint4* s0 = (const uint4*)(a.oper0 + (long)p * (OPER_BYTES / 2));
             const uint4* s1 = (const uint4*)((const unsigned char*)a.aoper + (long)p * AOPER2_STRIDE);
             const uint4* s2 = (const uint4*)((const unsigned char*)a.mf + (long)p * MF_BYTES);
-            for (int i = tid; i < KT_BYTES / 16; i += NTH) ((uint4*)(lds + AttnOff2::KT0))[i] = s0[KT_OFF / 16 + i];
-            for (int i = tid; i < VF_BYTES / 16; i += NTH) ((uint4*)(lds + AttnOff2::VF0))[i] = s0[VF_OFF / 16 + i];
-            for (int i = tid; i < AOPER2_BYTES / 16; i += NTH) ((uint4*)(lds + AttnOff2::QD2))[i] = s1[i];     // QD, QF contiguous
-            for (int i = tid; i < MF_BYTES / 16; i += NTH) ((uint4*)(lds + AttnOff2::MF2))[i] = s2[i];
-            for (int i = tid; i < 16; i += NTH) ((uint4*)(lds + AttnOff2::COLC))[i] = s1[AOPER2_BYTES / 16 + i];
+            for (int i = ptid; i < KT_BYTES / 16; i += NTH) ((uint4*)(lds + AttnOff2::KT0))[i] = s0[KT_OFF / 16 + i];
+            for (int i = ptid; i < VF_BYTES / 16; i += NTH) ((uint4*)(lds + AttnOff2::VF0))[i] = s0[VF_OFF / 16 + i];
+            for (int i = ptid; i < AOPER2_BYTES / 16; i += NTH) ((uint4*)(lds + AttnOff2::QD2))[i] = s1[i];     // QD, QF contiguous
+            for (int i = ptid; i < MF_BYTES / 16; i += NTH) ((uint4*)(lds + AttnOff2::MF2))[i] = s2[i];
+            for (int i = ptid; i < 16; i += NTH) ((uint4*)(lds + AttnOff2::COLC))[i] = s1[AOPER2_BYTES / 16 + i];
         }
         __syncthreads();
         AttnState st;
@@ -1106,6 +1246,7 @@ __global__ __launch_bounds__(64 * NW, 2) void i2t0_t2i_v2_kernel(FuseArgs2 a) {
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct) { st.m[ct] = NEG_BIG; st.l[ct] = 0.f; }
         uint4 b[8], qi[4], tk[4], tv[4];
+        const rsrc_t rh = make_rsrc(HAND ? a.hand + (long)p * HAND_PROMPT : nullptr, HAND ? (uint32_t)HAND_PROMPT : 0u);
 #define F2_LOAD0(tile_)                                                                            \
         do {                                                                                       \
             const int so_ = (tile_) * (16 * C * 2), to_ = (tile_) * (16 * CI * 2);                 \
@@ -1123,14 +1264,23 @@ __global__ __launch_bounds__(64 * NW, 2) void i2t0_t2i_v2_kernel(FuseArgs2 a) {
             _Pragma("unroll") for (int s_ = 0; s_ < 4; ++s_) tv[s_] = buf_load16(rtv, vvoff, to_ + s_ * 16);     \
         } while (0)
         F2_LOAD0(w);
-        ring_fill<G, Off>(ring, L, 0);
+#pragma unroll
+        for (int k = 0; k + 1 < Off::D; ++k) ring_fill<G, Off>(ring, L, k);
         for (int n = 0; n < NT; ++n) {
             asm volatile("" ::: "memory");
             const int nx = w + NW * (n + 1 < NT ? n + 1 : NT - 1), cur = w + NW * n;
             uint4 y1[8], pk0[2];
             float stat[2];
             i2t_block_r<G, Off, 0, false, 0, false>(ring, L, nullptr, a.eps, b, qi, wc, y1, [&]() { F2_LOAD1(cur); }, pk0, stat);
-            t2i_block_v2<G, Off, 40>(ring, L, y1, tk, tv, pk0, stat[0], stat[1], colc, gdl, st, [&]() { F2_LOAD2(cur); }, [&]() { F2_LOAD0(nx); });
+            t2i_block_v2<G, Off, 40>(ring, L, y1, tk, tv, pk0, stat[0], stat[1], colc, gdl, st, [&]() {
+                F2_LOAD2(cur);
+                // hand-over: registers the block holds anyway, the bits the stream kernel would recompute.  Behind the table load, so
+                // that no load the attention waits for is older than these stores (vmcnt counts in order)
+                if (HAND) {
+                    buf_store16(pk0[0], rh, voff, cur * HAND_TILE); buf_store16(pk0[1], rh, voff, cur * HAND_TILE + FRAG);
+                    if (fg == 0) buf_store8(make_uint2(__float_as_uint(stat[0]), __float_as_uint(stat[1])), rh, fr * 8, cur * HAND_TILE + HAND_STAT);
+                }
+            }, [&]() { F2_LOAD0(nx); });
 #pragma unroll
             for (int i = Off::USED; i < Off::N; ++i) RING_STEP(i);
         }
@@ -1141,16 +1291,17 @@ __global__ __launch_bounds__(64 * NW, 2) void i2t0_t2i_v2_kernel(FuseArgs2 a) {
         for (int ct = 0; ct < 4; ++ct) { st.l[ct] += __shfl_xor(st.l[ct], 16); st.l[ct] += __shfl_xor(st.l[ct], 32); }
         __syncthreads();
         float* mg = (float*)lds + w * MERGE_FLOATS;
-        if (fg == 0) {
+        const int mfr = plane & 15, mfg = plane >> 4;
+        if (mfg == 0) {
 #pragma unroll
-            for (int ct = 0; ct < 4; ++ct) { mg[ct * 16 + fr] = st.m[ct]; mg[64 + ct * 16 + fr] = st.l[ct]; }
+            for (int ct = 0; ct < 4; ++ct) { mg[ct * 16 + mfr] = st.m[ct]; mg[64 + ct * 16 + mfr] = st.l[ct]; }
         }
 #pragma unroll
         for (int h = 0; h < 8; ++h)
-            if ((fr >> 3) == (h & 1))
-                *(float4*)(mg + 128 + (h * 8 + (fr & 7)) * 16 + fg * 4) = make_float4(st.o[h][0], st.o[h][1], st.o[h][2], st.o[h][3]);
+            if ((mfr >> 3) == (h & 1))
+                *(float4*)(mg + 128 + (h * 8 + (mfr & 7)) * 16 + mfg * 4) = make_float4(st.o[h][0], st.o[h][1], st.o[h][2], st.o[h][3]);
         __syncthreads();
-        for (int idx = tid; idx < 512; idx += NTH) {
+        for (int idx = ptid; idx < 512; idx += NTH) {
             const int col = idx >> 3, d0 = (idx & 7) * 2, h = col >> 3, t = col & 7;
             const float* g0 = (const float*)lds;
             float mx = NEG_BIG;
@@ -1516,9 +1667,11 @@ extern "C" int msam_t2i_fold_values(const void* vtok0, int32_t P, int32_t Nt, co
     return msam_check_launch("fold_values");
 }
 extern "C" int64_t msam_i2t0_t2i_v2_workspace_bytes(int32_t P) { return (int64_t)P * AOPER2_STRIDE; }
-extern "C" int msam_i2t0_t2i_fused_v2(const void* tables, const void* tables2, const void* operands0, const void* mf, const float* ln0_w,
-                                      float ln_eps, const void* qtok, int32_t P, int32_t Nt, const void* wk, void* out,
-                                      void* workspace, int64_t workspace_bytes, void* stream) {
+extern "C" int64_t msam_chain_handover_bytes(int32_t P) { return (int64_t)P * HAND_PROMPT; }
+// handover: null = the kernel that writes nothing but `out`
+static int i2t0_t2i_v2_launch(const void* tables, const void* tables2, const void* operands0, const void* mf, const float* ln0_w,
+                              float ln_eps, const void* qtok, int32_t P, int32_t Nt, const void* wk, void* out,
+                              void* workspace, int64_t workspace_bytes, void* handover, void* stream) {
     if (!tables || !tables2 || !operands0 || !mf || !ln0_w || !qtok || !wk || !out || !workspace || P <= 0) {
         msam_set_error("msam_i2t0_t2i_fused_v2: null argument");
         return 1;
@@ -1535,13 +1688,26 @@ extern "C" int msam_i2t0_t2i_fused_v2(const void* tables, const void* tables2, c
     a.src = src; a.q0 = src + (long)T * C; a.tabk = a.q0 + (long)T * CI;
     a.tabv = (const u16*)(t2 + T2_TABV); a.gd = (const float*)(t2 + T2_GD); a.bwv = (const float*)(t2 + T2_BWV);
     a.oper0 = (const u16*)operands0; a.aoper = (const u16*)workspace; a.mf = (const u16*)mf; a.eps = ln_eps; a.Nt = Nt; a.P = P;
-    a.out = (u16*)out;
+    a.out = (u16*)out; a.hand = (unsigned char*)handover;
     const int cus = cu_count(), grid = P < cus ? P : cus;
     const double flops = (double)P * (T / 16) * 116.0 * 16384.0;          // 8 + 16 + 32 layer-0 block, 36 + 16 + 8 attention
-    msam_profile_mark2(stream, 1, flops, 0.0, 6);
-    hipLaunchKernelGGL((i2t0_t2i_v2_kernel<8, 4>), dim3(grid), dim3(512), 0, s, a);
-    msam_profile_mark2(stream, 0, flops, 0.0, 6);
+    const double bytes = handover ? (double)P * HAND_PROMPT : 0.0;
+    msam_profile_mark2(stream, 1, flops, bytes, 6);
+    if (handover) hipLaunchKernelGGL((i2t0_t2i_v2_kernel<8, 4, 3>), dim3(grid), dim3(512), 0, s, a);
+    else hipLaunchKernelGGL((i2t0_t2i_v2_kernel<8, 4>), dim3(grid), dim3(512), 0, s, a);
+    msam_profile_mark2(stream, 0, flops, bytes, 6);
     return msam_check_launch("i2t0_t2i_v2");
+}
+extern "C" int msam_i2t0_t2i_fused_v2(const void* tables, const void* tables2, const void* operands0, const void* mf, const float* ln0_w,
+                                      float ln_eps, const void* qtok, int32_t P, int32_t Nt, const void* wk, void* out,
+                                      void* workspace, int64_t workspace_bytes, void* stream) {
+    return i2t0_t2i_v2_launch(tables, tables2, operands0, mf, ln0_w, ln_eps, qtok, P, Nt, wk, out, workspace, workspace_bytes, nullptr, stream);
+}
+extern "C" int msam_i2t0_t2i_fused_v2_handover(const void* tables, const void* tables2, const void* operands0, const void* mf,
+                                               const float* ln0_w, float ln_eps, const void* qtok, int32_t P, int32_t Nt, const void* wk,
+                                               void* out, void* workspace, int64_t workspace_bytes, void* handover, void* stream) {
+    if (!handover) { msam_set_error("msam_i2t0_t2i_fused_v2_handover: null argument"); return 1; }
+    return i2t0_t2i_v2_launch(tables, tables2, operands0, mf, ln0_w, ln_eps, qtok, P, Nt, wk, out, workspace, workspace_bytes, handover, stream);
 }
 
 extern "C" int msam_i2t01_fused(const void* tables, const void* operands0, const float* ln0_w, const float* ln0_b,
@@ -1574,4 +1740,27 @@ extern "C" int msam_i2t01_fused(const void* tables, const void* operands0, const
     }
     msam_profile_mark2(stream, 0, flops, bytes, 7);
     return msam_check_launch("i2t01");
+}
+
+extern "C" int msam_i2t01_fused_handover(const void* tables, const void* operands0, const float* ln0_w, const float* ln0_b,
+                                         const void* operands1, const float* ln1_w, const float* ln1_b, float ln_eps,
+                                         int32_t P, int32_t Nt, const void* handover, void* out, void* stream) {
+    const u16* src = (const u16*)tables;
+    if (!src || !operands0 || !ln0_w || !ln0_b || !operands1 || !ln1_w || !ln1_b || !handover || !out || P <= 0) {
+        msam_set_error("msam_i2t01_fused_handover: null argument");
+        return 1;
+    }
+    if (Nt < 1 || Nt > 8) { msam_set_error("msam_i2t01_fused_handover: 1 <= Nt <= 8 tokens per prompt"); return 1; }
+    ChainArgs a{};
+    a.src = src; a.oper0 = (const u16*)operands0; a.ln0_w = ln0_w; a.ln0_b = ln0_b;
+    a.oper1 = (const u16*)operands1; a.tabq1 = src + (long)T * C + 2L * T * CI; a.ln1_w = ln1_w; a.ln1_b = ln1_b; a.eps = ln_eps;
+    a.Nt = Nt; a.P = P; a.out = (u16*)out; a.hand = (const unsigned char*)handover;
+    const int cus = cu_count(), grid = P < cus ? P : cus;
+    const double flops = (double)P * (T / 16) * 136.0 * 16384.0;        // executed: 48 (layer-0 half: residual + V'^T) + 88 (layer-1 block) MFMAs per tile
+    const double bytes = (double)P * T * C * 2 + (double)P * HAND_PROMPT;   // the layer-1 stream written, the hand-over read
+    msam_profile_mark2(stream, 1, flops, bytes, 7);
+    if (g_tune_chain_handover_ring == 2) hipLaunchKernelGGL((i2t01_hand_kernel<4, 2>), dim3(grid), dim3(NTHR8), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((i2t01_hand_kernel<4, 3>), dim3(grid), dim3(NTHR8), 0, (hipStream_t)stream, a);
+    msam_profile_mark2(stream, 0, flops, bytes, 7);
+    return msam_check_launch("i2t01_handover");
 }

@@ -625,7 +625,7 @@ extern "C" int msam_decoder_prepare_image(const msam_decoder_t* dec, const void*
                 nullptr, 0, 0, 0, c.pe_q[0], CI);
 }
 
-extern int g_tune_dec_chain, g_tune_dec_chain_min_p, g_tune_chain_variant;
+extern int g_tune_dec_chain, g_tune_dec_chain_min_p, g_tune_chain_variant, g_tune_chain_handover;
 // msam_tune_set "tok_fuse": 1 = product + LayerNorm + operand copies of the token side in one launch each (gemm_ln_tok: 18 fewer launches
 // per decode).  Measured (profiles/r03_experiments.md): 151.7 vs 154.4 tiles/s with one decode lane, 167.9 vs 168.7 with three - the
 // row-complete 64 x 256 tile kernel walks K = 2048 of the MLP on 112 workgroups and gives the saved launches back; the token side is
@@ -638,6 +638,7 @@ struct Work {
     float *qpe, *queries, *tmp; u16 *a, *b, *qs, *ks, *vs, *attn_tok, *mlp_h;
     u16 *keys, *kimg, *vT, *qimg, *attn_img, *up1; float* pre;
     u16 *hh0, *hh1; float *hyper, *iou_full;
+    void* hand;
 };
 long work_bytes(int P, int Nt) {
     const long M = (long)P * Nt, R = (long)P * T;
@@ -651,6 +652,7 @@ long work_bytes(int P, int Nt) {
     b += align256(R * C * 4);                     // pre
     b += 2 * align256(5L * P * C * 2);            // hh0, hh1 (one [P, 256] block per head)
     b += align256((long)P * 4 * 128 * 4) + align256((long)P * 128 * 4);
+    b += align256(msam_chain_handover_bytes(P));  // hand (chained form: layer-0 probabilities and statistics per tile, 2176 B each)
     return b;
 }
 Work carve_work(void* base, int P, int Nt) {
@@ -668,6 +670,7 @@ Work carve_work(void* base, int P, int Nt) {
     w.pre = (float*)take(R * C * 4);
     w.hh0 = (u16*)take(5L * P * C * 2); w.hh1 = (u16*)take(5L * P * C * 2);
     w.hyper = (float*)take((long)P * 4 * 128 * 4); w.iou_full = (float*)take((long)P * 128 * 4);
+    w.hand = take(msam_chain_handover_bytes(P));
     return w;
 }
 
@@ -825,6 +828,10 @@ int decoder_run(const msam_decoder_t* dec, const msam_mask_prompt_t* mask_w, con
     void* const tables2 = (char*)tables - msam_chain_tables2_bytes();
     void* const mfrag = (char*)oper0 + msam_i2t_fold_operand_bytes(P);
     if (chain2) CHECK(msam_chain_prepare_tables2_c(im.src_bf16, c.chain2, tables2, cx.s));
+    // hand-over (msam_tune_set "chain_handover"): the attention kernel of layer 1 stores the probabilities and LayerNorm statistics of
+    // its layer-0 block per tile in w.hand, the stream kernel at the end of layer 1 reads them instead of computing them again.  Both
+    // run on this stream, the token side of layer 1 between them: no other buffer of the workspace is free over that span
+    const bool handover = chain2 && g_tune_chain_handover != 0;
     for (int li = 0; li < nlayers && li < 2; ++li) {
         const msam_twoway_layer_t& L = dec->layer[li];
         // (1) token self attention
@@ -866,7 +873,10 @@ int decoder_run(const msam_decoder_t* dec, const msam_mask_prompt_t* mask_w, con
         } else if (chain) {
             const msam_twoway_layer_t& L0 = dec->layer[0];
             const int64_t avail = (int64_t)R * CI * 2 - msam_chain_tables_bytes() - msam_chain_tables2_bytes();
-            if (chain2)
+            if (handover)
+                CHECK(msam_i2t0_t2i_fused_v2_handover(tables, tables2, oper0, mfrag, L0.n4_w, 1e-5f, w.qs, P, Nt, L.t2i.k_w, w.attn_tok,
+                                                      w.vT, avail, w.hand, cx.s));
+            else if (chain2)
                 CHECK(msam_i2t0_t2i_fused_v2(tables, tables2, oper0, mfrag, L0.n4_w, 1e-5f, w.qs, P, Nt, L.t2i.k_w, w.attn_tok, w.vT,
                                              avail, cx.s));
             else
@@ -929,7 +939,10 @@ int decoder_run(const msam_decoder_t* dec, const msam_mask_prompt_t* mask_w, con
                 CHECK(msam_i2t_fold_operands(w.ks, w.vs, P, Nt, L.i2t.q_w, L.i2t.o_w, L.i2t.o_b, li, li == 0 ? oper0 : oper1, cx.s));
             if (li == 1) {
                 const msam_twoway_layer_t& L0 = dec->layer[0];
-                CHECK(msam_i2t01_fused(tables, oper0, L0.n4_w, L0.n4_b, oper1, L.n4_w, L.n4_b, 1e-5f, P, Nt, w.keys, cx.s));   // blocked stream
+                if (handover)
+                    CHECK(msam_i2t01_fused_handover(tables, oper0, L0.n4_w, L0.n4_b, oper1, L.n4_w, L.n4_b, 1e-5f, P, Nt, w.hand, w.keys, cx.s));
+                else
+                    CHECK(msam_i2t01_fused(tables, oper0, L0.n4_w, L0.n4_b, oper1, L.n4_w, L.n4_b, 1e-5f, P, Nt, w.keys, cx.s));   // blocked stream
             }
         } else if (Nt <= 8) {
             const bool shared = li == 0 && !own_src;

@@ -1116,6 +1116,56 @@ def i2t01_fused(tables, operands0, ln0_w, ln0_b, operands1, ln1_w, ln1_b, P: int
     return out
 
 
+def _chain_handover_buffer(P: int, device) -> torch.Tensor:
+    """Uninitialised hand-over buffer of the chained kernels for P prompts (include/msam_hip.h msam_chain_handover_bytes)."""
+    _need(P > 0, f"P = {P} must be positive")
+    return torch.empty((int(_lib.load().msam_chain_handover_bytes(P)),), dtype=torch.uint8, device=device)
+
+
+def _i2t0_t2i_fused_v2_handover(tables, tables2, operands0, mf, ln0_w, qtok, wk, handover, *, ln_eps: float = 1e-5):
+    """:func:`i2t0_t2i_fused_v2` that also fills ``handover`` (uint8, >= msam_chain_handover_bytes(P)) with the layer-0 probabilities
+    and LayerNorm statistics of every tile (include/msam_hip.h msam_i2t0_t2i_fused_v2_handover) -> [P,Nt,128]."""
+    dev = _home("tables", tables)
+    lib = _lib.load()
+    d16 = _lib.decoder_dtype()
+    _t("qtok", qtok, d16, (None, None, 128), dev)
+    P, Nt = qtok.shape[0], qtok.shape[1]
+    _blob("tables", tables, int(lib.msam_chain_tables_bytes()), dev)
+    _blob("tables2", tables2, int(lib.msam_chain_tables2_bytes()), dev)
+    _blob("operands0", operands0, int(lib.msam_i2t_fold_operand_bytes(P)), dev)
+    _blob("mf", mf, int(lib.msam_t2i_fold_values_bytes(P)), dev)
+    _blob("handover", handover, int(lib.msam_chain_handover_bytes(P)), dev)
+    _t("ln0_w", ln0_w, _F32, (256,), dev)
+    _t("wk", wk, d16, (128, 256), dev)
+    nbytes = int(lib.msam_i2t0_t2i_v2_workspace_bytes(P))
+    work = torch.empty((nbytes,), dtype=torch.uint8, device=qtok.device)
+    out = torch.empty((P, Nt, 128), dtype=d16, device=qtok.device)
+    _lib.check(lib.msam_i2t0_t2i_fused_v2_handover(tables.data_ptr(), tables2.data_ptr(), operands0.data_ptr(), mf.data_ptr(),
+                                                   ln0_w.data_ptr(), ln_eps, qtok.data_ptr(), P, Nt, wk.data_ptr(), out.data_ptr(),
+                                                   work.data_ptr(), nbytes, handover.data_ptr(), _lib.stream_ptr()),
+               "msam_i2t0_t2i_fused_v2_handover")
+    return out
+
+
+def _i2t01_fused_handover(tables, operands0, ln0_w, ln0_b, operands1, ln1_w, ln1_b, P: int, Nt: int, handover, *, ln_eps: float = 1e-5):
+    """:func:`i2t01_fused` on the ``handover`` buffer :func:`_i2t0_t2i_fused_v2_handover` filled for the same operands0 / tables
+    (include/msam_hip.h msam_i2t01_fused_handover) -> the layer-1 output stream [P,4096,256] in the BLOCKED layout."""
+    dev = _home("tables", tables)
+    lib = _lib.load()
+    _need(P > 0 and Nt > 0, f"P = {P} and Nt = {Nt} must be positive")
+    _blob("tables", tables, int(lib.msam_chain_tables_bytes()), dev)
+    _blob("operands0", operands0, int(lib.msam_i2t_fold_operand_bytes(P)), dev)
+    _blob("operands1", operands1, int(lib.msam_i2t_fold_operand_bytes(P)), dev)
+    _blob("handover", handover, int(lib.msam_chain_handover_bytes(P)), dev)
+    for name, t in (("ln0_w", ln0_w), ("ln0_b", ln0_b), ("ln1_w", ln1_w), ("ln1_b", ln1_b)):
+        _t(name, t, _F32, (256,), dev)
+    out = torch.empty((P, 4096, 256), dtype=_lib.decoder_dtype(), device=tables.device)
+    _lib.check(lib.msam_i2t01_fused_handover(tables.data_ptr(), operands0.data_ptr(), ln0_w.data_ptr(), ln0_b.data_ptr(),
+                                             operands1.data_ptr(), ln1_w.data_ptr(), ln1_b.data_ptr(), ln_eps, P, Nt,
+                                             handover.data_ptr(), out.data_ptr(), _lib.stream_ptr()), "msam_i2t01_fused_handover")
+    return out
+
+
 def upscale_fused(keys, w1, b1, ln_w, ln_b, w2, b2, hyper, mask0: int, nmask: int, *, ln_eps: float = 1e-6, blocked: bool = False,
                   centred: bool = False):
     """Fused output up-scaling + hyper-network product (include/msam_hip.h msam_upscale_fused).
