@@ -1012,6 +1012,53 @@ int msam_semantic_loss_backward(const float* logits, const int32_t* target, int3
 int msam_depth_conv3_bf16(const void* x, int64_t ldx, const void* w, const float* bias, float* out, int64_t ldc, int32_t B, int32_t D,
                           int32_t T, int32_t Ci, int32_t Co, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * The 3 x 3 x 3 convolution of the volumetric convolutional decoder (models/simple_sam_3d_wrapper.py: Conv3d(Ci, Co, 3, padding=1)) on
+ * channels-last voxel rows, as an implicit GEMM with K = 27 Ci (csrc/conv3d.hip): one launch, no im2col copy, no padded copy, no permute.
+ *   out[m, co] = bias[co] + sum_{tap, ci} w[co, tap Ci + ci] x[m + ((kz - 1) H + (ky - 1)) W + (kx - 1), ci],  tap = (kz 3 + ky) 3 + kx,
+ * a term dropped when the tap leaves the volume in z, y or x.
+ * x: bf16 [B D H W, Ci], row ((b D + z) H + y) W + x, row stride ldx (elements, >= Ci, a multiple of 8); w: bf16 [Co, Kp] contiguous with
+ * Kp = 27 Ci rounded up to a multiple of 64, tap-major (w[co, tap Ci + ci] = conv.weight[co, ci, kz, ky, kx]), columns >= 27 Ci zero;
+ * bias: fp32 [Co] or NULL; out: fp32 [B D H W, Co], row stride ldc (>= Co, a multiple of 4).  Ci % 8 == 0, 8 <= Ci <= 4096; Co % 16 == 0
+ * (a convolution with fewer output channels pads w with zero rows): the N tile is the largest of 128, 64, 32, 16 that divides Co.
+ * x and w below 2^31 bytes each; all pointers 16-byte aligned.  bf16 operands, fp32 accumulation in one fixed order: two calls agree
+ * bit for bit; no atomics.  No address outside x is formed.
+ * The input gradient is the same call: dX = conv(dY, W') with W'[ci, tap Co + co] = W[co, (26 - tap) Ci + ci].
+ * Any other argument: status 1 with the error text set, before any launch.  Kernel on `stream`, no synchronisation. */
+int msam_conv3d_k3_bf16(const void* x, int64_t ldx, const void* w, const float* bias, float* out, int64_t ldc, int32_t B, int32_t D,
+                        int32_t H, int32_t W, int32_t Ci, int32_t Co, void* stream);
+/* The weight gradient of that convolution: dw[tap Ci + ci, co] = sum_m x[m + shift(tap), ci] dy[m, co] over the voxels whose tap lies
+ * inside the volume.  x: bf16 [M, Ci] (ldx), dy: bf16 [M, Co] (ldy), both strides in eights, Ci and Co multiples of 8; dw: fp32
+ * [27 Ci, Co] contiguous.  The voxels are split over workgroups, the partial tiles go to `workspace` (msam_conv3d_k3_wgrad_workspace_bytes,
+ * -1 for arguments the call refuses) and are added in split order: no atomics, the same bits on every run. */
+int64_t msam_conv3d_k3_wgrad_workspace_bytes(int32_t B, int32_t D, int32_t H, int32_t W, int32_t Ci, int32_t Co);
+int msam_conv3d_k3_wgrad_bf16(const void* x, int64_t ldx, const void* dy, int64_t ldy, float* dw, void* workspace, int64_t workspace_bytes,
+                              int32_t B, int32_t D, int32_t H, int32_t W, int32_t Ci, int32_t Co, void* stream);
+
+/* InstanceNorm3d (no affine, no running statistics, biased variance) on fp32 channels-last rows [B V, C] (V = D H W voxels per volume,
+ * row strides in fours, C a power of two in 4 .. 1024, B V < 2^31).  Sums are accumulated in fp64 per workgroup into `workspace`
+ * (msam_instance_norm_workspace_bytes(B, V, C); -1 for arguments the calls refuse) and added in index order: no atomics.
+ *   _stats:    stats[b, c] = (mean, biased variance) as fp64 [B, C, 2]; V >= 2.
+ *   _apply:    y = act((a - mean_a) rstd_a + (r - mean_r) rstd_r), rstd = 1 / sqrt(var + eps); r (with stats_r) may be NULL, act is
+ *              LeakyReLU(slope) if has_act, else the identity; written to out32 (fp32) and / or out16 (bf16), either may be NULL.
+ *   _backward: with g = dy act'(pre), ahat / rhat the normalised operands and <.> the mean over a volume:
+ *              da = rstd_a (g - <g> - ahat <g ahat>), dr = rstd_r (g - <g> - rhat <g rhat>); one statistics pass (sums [B, C, 3] fp64 =
+ *              <g>, <g ahat>, <g rhat>) and one elementwise pass.
+ * msam_column_sums_f32: sums[c] = sum_m x[m, c] (fp64 [C]) by the statistics pass - the bias gradient of the convolution; workspace of
+ * msam_instance_norm_workspace_bytes(1, M, C). */
+int64_t msam_instance_norm_workspace_bytes(int32_t B, int64_t V, int32_t C);
+int msam_instance_norm_stats(const float* x, int64_t ldx, int32_t B, int64_t V, int32_t C, double* stats, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+int msam_instance_norm_apply(const float* a, int64_t lda, const double* stats_a, const float* r, int64_t ldr, const double* stats_r,
+                             int32_t B, int64_t V, int32_t C, float eps, float slope, int32_t has_act, float* out32, int64_t ld32,
+                             void* out16, int64_t ld16, void* stream);
+int msam_instance_norm_backward(const float* dy, int64_t ldy, const float* a, int64_t lda, const double* stats_a, const float* r,
+                                int64_t ldr, const double* stats_r, int32_t B, int64_t V, int32_t C, float eps, float slope,
+                                int32_t has_act, float* da, int64_t ldda, float* dr, int64_t lddr, double* sums, void* workspace,
+                                int64_t workspace_bytes, void* stream);
+int msam_column_sums_f32(const float* x, int64_t ldx, int64_t M, int32_t C, double* sums, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -274,6 +274,15 @@ _PROTOS = {
     "msam_semantic_loss_forward": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _i32, C.c_double, _vp, _i64, _vp, _vp, _vp]),
     "msam_semantic_loss_backward": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _i32, C.c_double, _vp, _vp, _vp, _vp]),
     "msam_depth_conv3_bf16": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "msam_conv3d_k3_bf16": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "msam_conv3d_k3_wgrad_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "msam_conv3d_k3_wgrad_bf16": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "msam_instance_norm_workspace_bytes": (_i64, [_i32, _i64, _i32]),
+    "msam_instance_norm_stats": (_i32, [_vp, _i64, _i32, _i64, _i32, _vp, _vp, _i64, _vp]),
+    "msam_instance_norm_apply": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i32, _i64, _i32, _f32, _f32, _i32, _vp, _i64, _vp, _i64, _vp]),
+    "msam_instance_norm_backward": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _i64, _i32, _f32, _f32, _i32, _vp, _i64, _vp, _i64,
+                                           _vp, _vp, _i64, _vp]),
+    "msam_column_sums_f32": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp]),
 }
 OPTIONAL = set()
 

@@ -15,7 +15,7 @@ the un-wrapped blocks.  The decoder takes all B D embeddings in one ``mask_decod
 embedding and ``no_mask_embed`` as the dense one, the reference's broadcast written out).
 
 Limits of this build: three classes (``modeling.MaskDecoder`` has three multi-mask outputs) and 1024 x 1024 slices (``build_sam``);
-``SimpleSam3DWrapper`` (a per-slice encoder with a 3 x 3 x 3 convolutional decoder) is not built.
+``models.simple_sam_3d_wrapper.SimpleSam3DWrapper`` (a per-slice encoder with a 3 x 3 x 3 convolutional decoder) takes any number of classes.
 PARITY: the depth convolution is pinned against torch's ``Conv3d`` (tests/depth_conv_ref.py) and the block against its fp64 restatement
 (tests/test_gpu_sam3d.py); the reference's wrapper itself could not be run (``segment_anything`` is not installed)."""
 from __future__ import annotations

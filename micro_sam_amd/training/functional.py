@@ -9,6 +9,10 @@ shapes and the tape, every forward / backward product runs a HIP kernel):
 * ``attention``   softmax(q k^T / sqrt(d)) v, ``msam_attention_forward`` / ``msam_attention_backward`` (fp32);
 * ``relpos_attention``  the image encoder's attention with its decomposed relative position bias on one token grid,
                   ``msam_relpos_attention_forward`` / ``_backward`` (fp32; gradients also for the two bias tensors).
+* ``conv3d_k3``   ``Conv3d(Ci, Co, 3, padding=1)`` on channels-last volumes, ``msam_conv3d_k3_bf16`` in both directions and
+                  ``msam_conv3d_k3_wgrad_bf16`` (bf16 operands, fp32 accumulation; the volumetric convolutional decoder);
+* ``instance_norm_act``  ``leaky_relu(InstanceNorm3d(a) [+ InstanceNorm3d(r)])``, ``msam_instance_norm_stats`` / ``_apply`` /
+                  ``_backward`` (fp32, fp64 sums).
 
 There is no CPU / eager fallback: on a machine without the library these raise.
 """
@@ -272,6 +276,150 @@ def depth_conv3(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, depth
     if isinstance(depth, bool) or not isinstance(depth, int) or depth < 1 or x.shape[0] % depth != 0:
         raise ValueError(f"depth_conv3: depth = {depth!r} must be a positive int that divides the {x.shape[0]} slices")
     return _DepthConv3.apply(x, weight, bias, depth)
+
+
+# bf16 operands of the 3 x 3 x 3 convolution per parameter and parameter version, as _WCONV16: the tap-major W [Co', Kp(Ci)] of the
+# forward pass and W' [Ci', Kp(Co)] (taps reversed, channels transposed) of the input gradient, rows zero-padded to the kernel's 16
+_WCONV27 = {}
+
+
+def _conv27_weight16(weight: torch.Tensor):
+    from .._conv3d import tap_major, tap_major_transposed
+
+    def make():
+        w16 = weight.detach().to(torch.bfloat16)
+        return tap_major(w16), tap_major_transposed(w16)
+    if not isinstance(weight, torch.nn.Parameter):
+        return make()
+    key = id(weight)
+    hit = _WCONV27.get(key)
+    stamp = (weight._version, weight.data_ptr(), weight.device.index)
+    if hit is not None and hit[0]() is weight and hit[1] == stamp:
+        return hit[2], hit[3]
+    if len(_WCONV27) > 1024:                 # parameters of discarded models
+        for k in [k for k, v in _WCONV27.items() if v[0]() is None]:
+            del _WCONV27[k]
+    w16, w16t = make()
+    _WCONV27[key] = (weakref.ref(weight), stamp, w16, w16t)
+    return w16, w16t
+
+
+class _Conv3dK3(torch.autograd.Function):
+    """``Conv3d(Ci, Co, 3, padding=1)`` on channels-last volumes (csrc/conv3d.hip).  Forward: the bf16 copy of x, then the implicit-GEMM
+    kernel.  Backward: the bf16 copy of dY; dX by the SAME kernel on W' (taps reversed, channels transposed); dW by the voxel-contracting
+    kernel on the two bf16 copies (no transposed or shifted copy is made); db by the fixed-order column sums of dY (fp32).  Every product
+    is one fixed-order sum: the same bits on every run."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        shape = x.shape
+        B, D, H, W, ci = (int(v) for v in shape)
+        co = int(weight.shape[0])
+        a16 = x.reshape(-1, ci).to(torch.bfloat16).contiguous()
+        w16, w16t = _conv27_weight16(weight)
+        b = None if bias is None else bias.detach().float().contiguous()
+        if b is not None and w16.shape[0] != co:
+            b = torch.nn.functional.pad(b, (0, w16.shape[0] - co))
+        y = ops.conv3d_k3(a16, w16, b, B, D, H, W)
+        if w16.shape[0] != co:
+            y = y[:, :co]                    # a view: the consumers take a row stride
+        ctx.save_for_backward(a16 if weight.requires_grad else None, w16t)
+        ctx.has_bias = bias is not None
+        ctx.geom = (shape, co)
+        return y.view(B, D, H, W, co)        # (splitting the rows of a column slice is still a view)
+
+    @staticmethod
+    def backward(ctx, dy):
+        a16, w16t = ctx.saved_tensors
+        shape, co = ctx.geom
+        B, D, H, W, ci = (int(v) for v in shape)
+        dy2 = dy.reshape(-1, co)
+        want_dx = ctx.needs_input_grad[0]
+        want_dw = ctx.needs_input_grad[1] and a16 is not None
+        want_db = ctx.has_bias and ctx.needs_input_grad[2]
+        dy16 = dy2.to(torch.bfloat16).contiguous() if (want_dx or want_dw) else None
+        dx = dw = db = None
+        if want_dx:
+            dx = ops.conv3d_k3(dy16, w16t, None, B, D, H, W)                        # dX = conv(dY, W')
+            if w16t.shape[0] != ci:
+                dx = dx[:, :ci]
+            dx = dx.reshape(shape)
+        if want_dw:
+            dw = ops.conv3d_k3_wgrad(a16, dy16, B, D, H, W)
+        if want_db:
+            d32 = dy2.float()
+            wide = 1 << max(2, (co - 1).bit_length())                               # the column sums take a power of two of columns
+            if wide != co:
+                d32 = torch.nn.functional.pad(d32, (0, wide - co))
+            db = ops.column_sums(d32.contiguous() if d32.stride(1) != 1 or d32.stride(0) % 4 else d32)[:co]
+        return dx, dw, db
+
+
+def conv3d_k3(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor = None) -> torch.Tensor:
+    """``nn.Conv3d(Ci, Co, 3, padding=1)`` on channels-last volumes: x fp32 [B, D, H, W, Ci], weight [Co, Ci, 3, 3, 3] (the module's
+    parameter shape), bias [Co] or None -> fp32 [B, D, H, W, Co].  bf16 operands, fp32 accumulation in both directions; Ci and Co are
+    multiples of 8.  (For Co % 16 != 0 the result is a view of the kernel's padded rows.)"""
+    if x.dim() != 5 or weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or x.shape[-1] != weight.shape[1]:
+        raise ValueError(f"conv3d_k3: x must be [B, D, H, W, Ci] and weight [Co, Ci, 3, 3, 3], got {tuple(x.shape)} and "
+                         f"{tuple(weight.shape)}")
+    if weight.shape[0] % 8 or weight.shape[1] % 8:
+        raise ValueError(f"conv3d_k3: Ci and Co must be multiples of 8, got weight {tuple(weight.shape)}")
+    if bias is not None and tuple(bias.shape) != (weight.shape[0],):
+        raise ValueError(f"conv3d_k3: bias must be [{weight.shape[0]}], got {tuple(bias.shape)}")
+    return _Conv3dK3.apply(x, weight, bias)
+
+
+def _rows_view(t: torch.Tensor):
+    """[B, ..., C] fp32 -> its row matrix [B V, C] without a copy where the rows are evenly strided (a column slice of padded rows)."""
+    c = t.shape[-1]
+    t = t.float()
+    if t.is_contiguous():
+        return t.view(-1, c)
+    ld = t.stride(-2)
+    ok = t.stride(-1) == 1 and ld % 4 == 0 and t.data_ptr() % 16 == 0
+    for d in range(t.dim() - 2, 0, -1):
+        ok = ok and t.stride(d - 1) == t.stride(d) * t.shape[d]
+    if ok:
+        return t.as_strided((t.numel() // c, c), (ld, 1))
+    return t.contiguous().view(-1, c)
+
+
+class _InstanceNormAct(torch.autograd.Function):
+    """``leaky_relu(instance_norm(a) [+ instance_norm(residual)])`` on channels-last volumes (csrc/conv3d.hip): one statistics pass per
+    operand and one fused elementwise pass; backward by its closed form, one statistics pass and one elementwise pass."""
+
+    @staticmethod
+    def forward(ctx, a, residual, negative_slope, eps):
+        shape = a.shape
+        B, c = int(shape[0]), int(shape[-1])
+        V = a.numel() // (B * c)
+        a2 = _rows_view(a)
+        sa = ops.instance_norm_stats(a2, B, V)
+        r2 = sr = None
+        if residual is not None:
+            r2 = _rows_view(residual)
+            sr = ops.instance_norm_stats(r2, B, V)
+        y, _ = ops.instance_norm_apply(a2, sa, B, V, r2, sr, negative_slope, eps)
+        ctx.save_for_backward(a2, sa, r2, sr)
+        ctx.conf = (shape, B, V, negative_slope, eps)
+        return y.view(shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        a2, sa, r2, sr = ctx.saved_tensors
+        shape, B, V, negative_slope, eps = ctx.conf
+        da, dr = ops.instance_norm_backward(_rows_view(dy), a2, sa, B, V, r2, sr, negative_slope, eps)
+        return da.view(shape), None if dr is None else dr.view(shape), None, None
+
+
+def instance_norm_act(a: torch.Tensor, residual: torch.Tensor = None, negative_slope=0.01, eps: float = 1e-5) -> torch.Tensor:
+    """``nn.InstanceNorm3d`` (no affine, no running statistics) of channels-last volumes a [B, D, H, W, C], optionally plus the
+    InstanceNorm of ``residual`` (same shape), then ``LeakyReLU(negative_slope)`` (None: no activation) -> fp32 [B, D, H, W, C].  C is a
+    power of two in 4 .. 1024; a volume of fewer than 2 voxels raises ``ValueError``."""
+    if a.dim() < 3 or (residual is not None and residual.shape != a.shape):
+        raise ValueError(f"instance_norm_act: a must be [B, ..., C] and residual of the same shape, got {tuple(a.shape)} and "
+                         f"{None if residual is None else tuple(residual.shape)}")
+    return _InstanceNormAct.apply(a, residual, negative_slope, eps)
 
 
 class _LayerNorm(torch.autograd.Function):
