@@ -1000,7 +1000,7 @@ int msam_semantic_loss_backward(const float* logits, const int32_t* target, int3
 
 /* ---------------------------------------------------------------------------------------------------
  * The depth convolution of the 3-d adapter (micro_sam/models/sam_3d_wrapper.py NDBlockWrapper: Conv3d(C, C, kernel_size=(3, 1, 1),
- * padding="same")) on token-major rows, as an implicit-shift MFMA GEMM (csrc/depthconv.hip): one launch, no im2col copy, no permute.
+ * padding="same")) on token-major rows, as an implicit-shift MFMA GEMM (csrc/conv3d.hip): one launch, no im2col copy, no permute.
  *   out[b, z, t, :] = bias + sum_{j = 0..2} W_j x[b, z + j - 1, t, :]      (a term is dropped when z + j - 1 is outside [0, D))
  * x: bf16 [B D T, Ci], row (b D + z) T + t, row stride ldx (elements, >= Ci, a multiple of 8); w: bf16 [Co, 3 Ci] contiguous, tap-major
  * (columns j Ci .. (j + 1) Ci - 1 are tap j, i.e. w[co, j Ci + ci] = conv.weight[co, ci, j, 0, 0]); bias: fp32 [Co] or NULL; out: fp32

@@ -1,6 +1,7 @@
 """``ops.conv3d_k3``, ``ops.conv3d_k3_wgrad``, ``ops.instance_norm_stats``, ``ops.instance_norm_apply``, ``ops.instance_norm_backward`` and
 ``ops.column_sums``: the Python side of csrc/conv3d.hip, the 3 x 3 x 3 convolution and the InstanceNorm of the volumetric convolutional
-decoder (``models.simple_sam_3d_wrapper``) on channels-last voxel rows [B D H W, C].  Defined here and re-exported by micro_sam_amd/ops.py
+decoder (``models.simple_sam_3d_wrapper``) on channels-last voxel rows [B D H W, C]; ``_forward_operands`` also serves the file's other
+forward entry, ``_depthconv.depth_conv3``.  Defined here and re-exported by micro_sam_amd/ops.py
 with the boundary checks of the other wrappers (``ops._home`` / ``ops._t`` / ``ops._need``); every check runs before the launch.
 tests/test_conv3d_host.py, tests/test_gpu_conv3d.py, tests/test_instnorm_host.py and tests/test_gpu_instnorm.py run them."""
 from __future__ import annotations
@@ -54,30 +55,43 @@ def _stride(t: torch.Tensor) -> int:
     return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
 
 
-def conv3d_k3(x16: torch.Tensor, w16: torch.Tensor, bias: Optional[torch.Tensor], B: int, D: int, H: int, W: int,
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``Conv3d(Ci, Co, 3, padding=1)`` in one launch (msam_conv3d_k3_bf16): ``x16`` bf16 [B D H W, Ci] with contiguous rows (a row
-    stride in eights), ``w16`` bf16 [Co', padded_k(Ci)] (``tap_major``), ``bias`` fp32 [Co'] or None -> fp32 [B D H W, Co'] (``out``:
-    written in place).  Ci % 8 == 0, Co' % 16 == 0.  Two calls agree bit for bit."""
+def _forward_operands(x16, w16, bias, out, *, dims: dict, ci_ok, ci_text: str, row_len, co_step: int):
+    """The checks ``conv3d_k3`` and ``depth_conv3`` share, in their order: the device, the int dims (their product is the number of rows),
+    the bf16 rows, the channels (``ci_ok`` / ``ci_text``: the caller's rule), the weight [a positive multiple of ``co_step``,
+    ``row_len(Ci)``], alignment, the byte limits, the optional bias and the optional ``out`` -> (ldx, Ci, Co, the bias pointer, out)."""
     from . import ops
     dev = ops._home("x16", x16)
-    _dims(B=B, D=D, H=H, W=W)
-    ops._t("x16", x16, torch.bfloat16, (B * D * H * W, None), dev, rows=True)
+    _dims(**dims)
+    rows = 1
+    for v in dims.values():
+        rows *= v
+    ops._t("x16", x16, torch.bfloat16, (rows, None), dev, rows=True)
     m, ci = (int(v) for v in x16.shape)
-    ops._need(8 <= ci <= 4096 and ci % 8 == 0, f"x16 must hold a multiple of 8 channels in 8 .. 4096, got {list(x16.shape)}")
-    ops._t("w16", w16, torch.bfloat16, (None, padded_k(ci)), dev)
+    ops._need(ci_ok(ci), f"x16 must hold {ci_text}, got {list(x16.shape)}")
+    ops._t("w16", w16, torch.bfloat16, (None, row_len(ci)), dev)
     co = int(w16.shape[0])
-    ops._need(co >= 16 and co % 16 == 0, f"w16 must hold a positive multiple of 16 rows, got {list(w16.shape)}")
+    ops._need(co >= co_step and co % co_step == 0, f"w16 must hold a positive multiple of {co_step} rows, got {list(w16.shape)}")
     ldx = _stride(x16)
     ops._need(ldx % 8 == 0 and x16.data_ptr() % 16 == 0 and w16.data_ptr() % 16 == 0,
               f"x16 and w16 must be 16-byte aligned with a row stride in eights, got a stride of {ldx}")
-    ops._need(m * ldx * 2 < 2 ** 31 and co * padded_k(ci) * 2 < 2 ** 31, f"x16 and w16 must stay below 2^31 bytes, got {m} rows of {ldx}")
+    ops._need(m * ldx * 2 < 2 ** 31 and co * row_len(ci) * 2 < 2 ** 31, f"x16 and w16 must stay below 2^31 bytes, got {m} rows of {ldx}")
     bias_ptr = ops._opt("bias", bias, torch.float32, (co,), dev)
     ops._need(bias is None or bias_ptr % 16 == 0, "bias must be 16-byte aligned")
     if out is None:
         out = torch.empty((m, co), dtype=torch.float32, device=dev)
     ops._t("out", out, torch.float32, (m, co), dev)
     ops._need(out.data_ptr() % 16 == 0, "out must be 16-byte aligned")
+    return ldx, ci, co, bias_ptr, out
+
+
+def conv3d_k3(x16: torch.Tensor, w16: torch.Tensor, bias: Optional[torch.Tensor], B: int, D: int, H: int, W: int,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``Conv3d(Ci, Co, 3, padding=1)`` in one launch (msam_conv3d_k3_bf16): ``x16`` bf16 [B D H W, Ci] with contiguous rows (a row
+    stride in eights), ``w16`` bf16 [Co', padded_k(Ci)] (``tap_major``), ``bias`` fp32 [Co'] or None -> fp32 [B D H W, Co'] (``out``:
+    written in place).  Ci % 8 == 0, Co' % 16 == 0.  Two calls agree bit for bit."""
+    ldx, ci, co, bias_ptr, out = _forward_operands(x16, w16, bias, out, dims=dict(B=B, D=D, H=H, W=W),
+                                                   ci_ok=lambda c: 8 <= c <= 4096 and c % 8 == 0,
+                                                   ci_text="a multiple of 8 channels in 8 .. 4096", row_len=padded_k, co_step=16)
     _lib.check(_lib.load().msam_conv3d_k3_bf16(x16.data_ptr(), ldx, w16.data_ptr(), bias_ptr, out.data_ptr(), co, B, D, H, W, ci, co,
                                                _lib.stream_ptr()), "msam_conv3d_k3_bf16")
     return out

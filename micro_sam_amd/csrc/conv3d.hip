@@ -1,17 +1,25 @@
-// The 3 x 3 x 3 convolutions and the InstanceNorm of the volumetric convolutional decoder (models/simple_sam_3d_wrapper.py: BasicBlock,
-// SegmentationHead) on CHANNELS-LAST voxel rows: a tensor [B, D, H, W, C] is the row matrix [B D H W, C], row ((b D + z) H + y) W + x.
+// The convolutions of the two 3-d wrappers as implicit GEMMs on bf16 rows [M, Ci], and the InstanceNorm of the volumetric decoder:
+//   * msam_conv3d_k3_bf16: Conv3d(Ci, Co, 3, padding=1) of models/simple_sam_3d_wrapper.py (BasicBlock, SegmentationHead) on
+//     CHANNELS-LAST voxel rows - a tensor [B, D, H, W, C] is the row matrix [B D H W, C], row ((b D + z) H + y) W + x;
+//   * msam_depth_conv3_bf16: Conv3d(C, C, (3, 1, 1), padding="same") of models/sam_3d_wrapper.py (NDBlockWrapper) on TOKEN-MAJOR rows
+//     [B D T, C], row (b D + z) T + t.
 //
-// 1. msam_conv3d_k3_bf16: Conv3d(Ci, Co, 3, padding=1) as an implicit GEMM with K = 27 Ci,
-//        out[m, co] = bias[co] + sum_{tap, ci} W[co, tap Ci + ci] x[m + shift(tap), ci],   tap = (kz 3 + ky) 3 + kx,
-//        shift(tap) = ((kz - 1) H + (ky - 1)) W + (kx - 1) rows, a term dropped when the tap leaves the volume in z, y or x.
-//    A (the im2col matrix [M, 27 Ci]) is never written.  The tile body is depthconv.hip's (128 x BN x 64, 256 threads, mfma16, swizzled
-//    LDS, register staging two k-tiles ahead, XCD remap) with two generalisations:
-//    * the A-side address: every staged row carries a 27-bit validity mask, and the tap is chosen PER 16-BYTE CHUNK (k = tap Ci + ci with
-//      Ci % 8 == 0, so a chunk never straddles two taps, but with Ci < 64 one 64-wide k-tile does).  A chunk whose tap lies outside the
-//      volume, whose row is past M or whose k lies in the padding of K is loaded from a LEGAL address - channel 0 of its own row, the row
-//      clamped to M - 1 - and zeroed in registers; no address outside x is formed;
-//    * the N tile: BN = 128 (2 x 2 waves of 4 x 4 fragments), 64, 32, 16 (4 x 1 waves of 2 x 4 / 2 x 2 / 2 x 1) from one template,
-//      chosen by the launcher as the largest that divides Co.
+// 1. The forward tile body, conv_taps_kernel<Geom, WM, WN, FM, FN>: K = TAPS Ci (rounded up to the k-tile of 64),
+//        out[m, co] = bias[co] + sum_{tap, ci} W[co, tap Ci + ci] x[m + tap_rows(tap), ci],   a term dropped when the tap leaves the volume.
+//    A (the im2col matrix [M, TAPS Ci]) is never written.  128 x BN x 64 tiles, 256 threads, v_mfma_f32_16x16x32_bf16, two LDS buffers with
+//    XOR-swizzled 128-B rows (common.h swz), global -> VGPR two k-tiles ahead -> ds_write, C staged through LDS for 16-byte stores, XCD
+//    remap.
+//    * A geometry (CubeGeom, DepthGeom) supplies the number of taps, a row's mask of the taps inside its volume, the tap of a k and the
+//      rows from a voxel to its neighbour of a tap; nothing else in the body depends on it.
+//        cube:  TAPS = 27, tap = (kz 3 + ky) 3 + kx, tap_rows = ((kz - 1) H + (ky - 1)) W + (kx - 1)
+//        depth: TAPS = 3,  tap = kz,                 tap_rows = (kz - 1) T        (T need not divide the tile: the mask is per row)
+//    * The A-side address: every staged row carries its mask, and the tap is chosen PER 16-BYTE CHUNK (k = tap Ci + ci with Ci % 8 == 0,
+//      so a chunk never straddles two taps, but with Ci < 64 one 64-wide k-tile does).  A chunk whose tap lies outside the volume, whose
+//      row is past M or whose k lies in the padding of K is loaded from a LEGAL address - channel 0 of its own row, the row clamped to
+//      M - 1 - and zeroed in registers; no address outside x is formed, also not for the first slice of the first volume and the last
+//      slice of the last one.
+//    * The N tile: BN = 128 (2 x 2 waves of 4 x 4 fragments), 64, 32, 16 (4 x 1 waves of 2 x 4 / 2 x 2 / 2 x 1) from one template.  The
+//      cube launcher takes the largest that divides Co; the depth launcher always 128.
 //    The input gradient is the same call on W' (include/msam_hip.h).
 // 2. msam_conv3d_k3_wgrad_bf16: dW[tap Ci + ci, co] = sum_m x[m + shift(tap), ci] dy[m, co], the same implicit A contracted over the
 //    voxels.  Both operands are channels-last, i.e. strided along the contraction: a workgroup stages 64 voxels of a 64-wide k-tile of A
@@ -65,10 +73,36 @@ MSAM_DEVINL int c3_tap_rows(int tap, int H, int W) {
     return ((kz - 1) * H + (ky - 1)) * W + (kx - 1);
 }
 
-template <int WM, int WN, int FM, int FN>
-__global__ __launch_bounds__(256, 2) void conv3d_k3_kernel(const u16* __restrict__ X, long ldx, const u16* __restrict__ Wt,
+// The geometries of conv_taps_kernel.  row_mask(m): bit tap set = voxel row m reads tap inside its volume; tap_of(k): the tap of column k
+// of A (>= TAPS in the padding of K); tap_rows(tap): rows from a voxel to its neighbour of tap (tap < TAPS)
+struct CubeGeom {
+    static constexpr int TAPS = 27;
+    int D, H, W;
+    unsigned magic;                                        // of Ci <= C3_MAX_CI (c3_div)
+    __device__ __forceinline__ int row_mask(int m) const { return c3_row_mask(m, D, H, W); }
+    __device__ __forceinline__ int tap_of(int k) const { return c3_div(k, magic); }
+    __device__ __forceinline__ int tap_rows(int tap) const { return c3_tap_rows(tap, H, W); }
+};
+
+struct DepthGeom {                                         // K = 3 Ci exactly: no padding, and two compares are exact for every Ci
+    static constexpr int TAPS = 3;
+    int D, T, Ci;
+    __device__ __forceinline__ int row_mask(int m) const {
+        const int z = (m / T) % D;
+        return (z > 0 ? 1 : 0) | 2 | (z < D - 1 ? 4 : 0);
+    }
+    // Ci % 64 == 0: a k-tile never mixes taps, so the tap is that of the k-tile's first column - one scalar value per k-tile
+    __device__ __forceinline__ int tap_of(int k) const {
+        const int k0 = k & ~(C3_BK - 1);
+        return (k0 >= Ci ? 1 : 0) + (k0 >= 2 * Ci ? 1 : 0);
+    }
+    __device__ __forceinline__ int tap_rows(int tap) const { return (tap - 1) * T; }
+};
+
+template <class Geom, int WM, int WN, int FM, int FN>
+__global__ __launch_bounds__(256, 2) void conv_taps_kernel(const u16* __restrict__ X, long ldx, const u16* __restrict__ Wt,
                                                            const float* __restrict__ bias, float* __restrict__ out, long ldc, int M,
-                                                           int D, int H, int W, int Ci, int Co, int Kp, unsigned magic) {
+                                                           int Ci, int Co, int Kp, Geom geom) {
     constexpr int BN = WN * FN * 16;
     constexpr int BCH = BN * 8;                            // 16-B chunks of a W tile
     constexpr int WP = (BCH + 255) / 256;                  // ... per thread
@@ -97,7 +131,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_kernel(const u16* __restrict
         const int row = p * 32 + srow;
         const int m = m0 + row;
         const int ar = m > M - 1 ? M - 1 : m;
-        ok[p] = m < M ? c3_row_mask(ar, D, H, W) : 0;
+        ok[p] = m < M ? geom.row_mask(ar) : 0;
         aoff[p] = (int)((long)ar * ldx * 2);
         ak[p] = (scp ^ swz(row)) * 8;
     }
@@ -145,15 +179,18 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_kernel(const u16* __restrict
     const rsrc_t rx = make_rsrc(X, (uint32_t)((((long)M - 1) * ldx + Ci) * 2));
     const rsrc_t rw = make_rsrc(Wt, (uint32_t)((long)Co * Kp * 2));
     // k-tile kt: chunk p of this thread holds k = kt 64 + ak[p] .. + 7 = channels ci .. ci + 7 of tap k / Ci.  A chunk that counts reads
-    // row m + shift(tap) (inside x: the mask says so); any other chunk channel 0 of its own row.  keep: bit p = chunk p counts
+    // row m + tap_rows(tap) (inside x: the mask says so); any other chunk channel 0 of its own row.  keep: bit p = chunk p counts
     auto load = [&](uint4 (&a)[4], uint4 (&w)[WP], int& keep, int kt) {
         keep = 0;
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             const int k = kt * C3_BK + ak[p];
-            const int tap = c3_div(k, magic);
-            const bool on = tap < 27 && ((ok[p] >> (tap & 31)) & 1);
-            const int rel = on ? c3_tap_rows(tap, H, W) * ldx2 + (k - tap * Ci) * 2 : 0;
+            const int tap = geom.tap_of(k);
+            const bool on = tap < Geom::TAPS && ((ok[p] >> (tap & 31)) & 1);
+            // worked out for every chunk and masked, not selected: a thread's four chunks share k, so they share this value, and the
+            // compiler keeps it out of an exec-mask region per load (unsigned: the value of a chunk that does not count may wrap)
+            const unsigned off = (unsigned)geom.tap_rows(tap) * (unsigned)ldx2 + (unsigned)(k - tap * Ci) * 2u;
+            const int rel = (int)(off & (on ? ~0u : 0u));
             a[p] = buf_load16(rx, aoff[p] + rel, 0);
             keep |= (on ? 1 : 0) << p;
         }
@@ -172,7 +209,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_kernel(const u16* __restrict
     };
     uint4 ra[4], rwv[WP], sa[4], swv[WP];
     int rkeep, skeep = 0;
-    // register staging TWO k-tiles ahead (two register sets, roles swapped by the 2x unrolled loop), as depthconv.hip; nk >= 4 always
+    // register staging TWO k-tiles ahead (two register sets, roles swapped by the 2x unrolled loop), as gemm.hip; nk >= 3 always
     load(ra, rwv, rkeep, 0);
     commit(ra, rwv, rkeep, 0);
     load(ra, rwv, rkeep, 1);
@@ -546,10 +583,48 @@ int64_t in_ws_bytes(int B, int64_t V, int C) { return (int64_t)B * in_plan(V, C)
 
 }  // namespace
 
+// The checks msam_conv3d_k3_bf16 and msam_depth_conv3_bf16 share, in the order null pointers (conv_null_check; the entry's own shape rules
+// come next), strides, 2^31 limits, alignment.  `who`: the entry's name; `rows`: how it spells M; Kp: the row length of W; BN: its N tile
+static int conv_null_check(const char* who, const void* x, const void* w, const void* out) {
+    char msg[128];
+    if (x && w && out) return 0;
+    snprintf(msg, sizeof msg, "%s: null pointer", who);
+    msam_set_error(msg);
+    return 1;
+}
+
+static int conv_operand_check(const char* who, const char* rows, const void* x, int64_t ldx, const void* w, const float* bias,
+                              const float* out, int64_t ldc, int64_t M, int32_t Ci, int32_t Co, int64_t Kp, int BN) {
+    char msg[384];
+    if (ldx < Ci || ldc < Co || ldx % 8 != 0 || ldc % 4 != 0) {
+        snprintf(msg, sizeof msg, "%s: needs ldx >= Ci in eights and ldc >= Co in fours, got ldx = %lld, ldc = %lld", who, (long long)ldx,
+                 (long long)ldc);
+        msam_set_error(msg);
+        return 1;
+    }
+    if (M >= (1LL << 31) || M * ldx * 2 >= (1LL << 31) || (int64_t)Co * Kp * 2 >= (1LL << 31) ||
+        ((M + C3_BM - 1) / C3_BM) * (Co / BN) >= (1LL << 31)) {
+        snprintf(msg, sizeof msg, "%s: x (%s rows of ldx) and W must stay below 2^31 bytes each, got %lld rows of %lld", who, rows,
+                 (long long)M, (long long)ldx);
+        msam_set_error(msg);
+        return 1;
+    }
+    if ((uintptr_t)x % 16 != 0 || (uintptr_t)w % 16 != 0 || (uintptr_t)out % 16 != 0 || (bias && (uintptr_t)bias % 16 != 0)) {
+        snprintf(msg, sizeof msg, "%s: x, w, bias and out must be 16-byte aligned", who);
+        msam_set_error(msg);
+        return 1;
+    }
+    return 0;
+}
+
+#define CONV_LAUNCH(GEOM_, WM_, WN_, FM_, FN_, geom_)                                                                                    \
+    hipLaunchKernelGGL((conv_taps_kernel<GEOM_, WM_, WN_, FM_, FN_>), dim3(tiles), dim3(256), 0, (hipStream_t)stream, (const u16*)x,     \
+                       (long)ldx, (const u16*)w, bias, out, (long)ldc, (int)M, (int)Ci, (int)Co, (int)Kp, geom_)
+
 extern "C" int msam_conv3d_k3_bf16(const void* x, int64_t ldx, const void* w, const float* bias, float* out, int64_t ldc, int32_t B,
                                    int32_t D, int32_t H, int32_t W, int32_t Ci, int32_t Co, void* stream) {
     char msg[384];
-    if (!x || !w || !out) { msam_set_error("msam_conv3d_k3_bf16: null pointer"); return 1; }
+    if (conv_null_check("msam_conv3d_k3_bf16", x, w, out)) return 1;
     if (B < 1 || D < 1 || H < 1 || W < 1 || Ci < 8 || Ci % 8 != 0 || Ci > C3_MAX_CI || Co < 16 || Co % 16 != 0) {
         snprintf(msg, sizeof msg, "msam_conv3d_k3_bf16: needs B, D, H, W >= 1, Ci a multiple of 8 in 8 .. %d and Co a positive multiple of 16, "
                                   "got B = %d, D = %d, H = %d, W = %d, Ci = %d, Co = %d", C3_MAX_CI, B, D, H, W, Ci, Co);
@@ -558,36 +633,36 @@ extern "C" int msam_conv3d_k3_bf16(const void* x, int64_t ldx, const void* w, co
     }
     const int64_t M = (int64_t)B * D * H * W;
     const int64_t Kp = ((int64_t)27 * Ci + 63) / 64 * 64;
-    if (ldx < Ci || ldc < Co || ldx % 8 != 0 || ldc % 4 != 0) {
-        snprintf(msg, sizeof msg, "msam_conv3d_k3_bf16: needs ldx >= Ci in eights and ldc >= Co in fours, got ldx = %lld, ldc = %lld",
-                 (long long)ldx, (long long)ldc);
-        msam_set_error(msg);
-        return 1;
-    }
     const int BN = Co % 128 == 0 ? 128 : Co % 64 == 0 ? 64 : Co % 32 == 0 ? 32 : 16;
-    if (M >= (1LL << 31) || M * ldx * 2 >= (1LL << 31) || (int64_t)Co * Kp * 2 >= (1LL << 31) ||
-        ((M + C3_BM - 1) / C3_BM) * (Co / BN) >= (1LL << 31)) {
-        snprintf(msg, sizeof msg, "msam_conv3d_k3_bf16: x (B D H W rows of ldx) and W must stay below 2^31 bytes each, got %lld rows of %lld",
-                 (long long)M, (long long)ldx);
-        msam_set_error(msg);
-        return 1;
-    }
-    if ((uintptr_t)x % 16 != 0 || (uintptr_t)w % 16 != 0 || (uintptr_t)out % 16 != 0 || (bias && (uintptr_t)bias % 16 != 0)) {
-        msam_set_error("msam_conv3d_k3_bf16: x, w, bias and out must be 16-byte aligned");
-        return 1;
-    }
+    if (conv_operand_check("msam_conv3d_k3_bf16", "B D H W", x, ldx, w, bias, out, ldc, M, Ci, Co, Kp, BN)) return 1;
     const unsigned tiles = (unsigned)(((M + C3_BM - 1) / C3_BM) * (Co / BN));
-    const unsigned magic = (unsigned)((1ULL << 32) / (unsigned)Ci + 1);
-#define C3_LAUNCH(WM_, WN_, FM_, FN_)                                                                                                   \
-    hipLaunchKernelGGL((conv3d_k3_kernel<WM_, WN_, FM_, FN_>), dim3(tiles), dim3(256), 0, (hipStream_t)stream, (const u16*)x, (long)ldx,  \
-                       (const u16*)w, bias, out, (long)ldc, (int)M, (int)D, (int)H, (int)W, (int)Ci, (int)Co, (int)Kp, magic)
-    if (BN == 128) C3_LAUNCH(2, 2, 4, 4);
-    else if (BN == 64) C3_LAUNCH(4, 1, 2, 4);
-    else if (BN == 32) C3_LAUNCH(4, 1, 2, 2);
-    else C3_LAUNCH(4, 1, 2, 1);
-#undef C3_LAUNCH
+    const CubeGeom geom = {(int)D, (int)H, (int)W, (unsigned)((1ULL << 32) / (unsigned)Ci + 1)};
+    if (BN == 128) CONV_LAUNCH(CubeGeom, 2, 2, 4, 4, geom);
+    else if (BN == 64) CONV_LAUNCH(CubeGeom, 4, 1, 2, 4, geom);
+    else if (BN == 32) CONV_LAUNCH(CubeGeom, 4, 1, 2, 2, geom);
+    else CONV_LAUNCH(CubeGeom, 4, 1, 2, 1, geom);
     return msam_check_launch("msam_conv3d_k3_bf16");
 }
+
+extern "C" int msam_depth_conv3_bf16(const void* x, int64_t ldx, const void* w, const float* bias, float* out, int64_t ldc, int32_t B,
+                                     int32_t D, int32_t T, int32_t Ci, int32_t Co, void* stream) {
+    char msg[384];
+    if (conv_null_check("msam_depth_conv3_bf16", x, w, out)) return 1;
+    if (B < 1 || D < 1 || T < 1 || Ci < 64 || Co < 128 || Ci % 64 != 0 || Co % 128 != 0) {
+        snprintf(msg, sizeof msg, "msam_depth_conv3_bf16: needs B, D, T >= 1, Ci a positive multiple of 64 and Co a positive multiple of "
+                                  "128, got B = %d, D = %d, T = %d, Ci = %d, Co = %d", B, D, T, Ci, Co);
+        msam_set_error(msg);
+        return 1;
+    }
+    const int64_t M = (int64_t)B * D * T;
+    const int64_t Kp = (int64_t)3 * Ci;                    // a multiple of the k-tile: no padding
+    if (conv_operand_check("msam_depth_conv3_bf16", "B D T", x, ldx, w, bias, out, ldc, M, Ci, Co, Kp, 128)) return 1;
+    const unsigned tiles = (unsigned)(((M + C3_BM - 1) / C3_BM) * (Co / 128));
+    const DepthGeom geom = {(int)D, (int)T, (int)Ci};
+    CONV_LAUNCH(DepthGeom, 2, 2, 4, 4, geom);
+    return msam_check_launch("msam_depth_conv3_bf16");
+}
+#undef CONV_LAUNCH
 
 static int wgrad_check(const char* who, int32_t B, int32_t D, int32_t H, int32_t W, int32_t Ci, int32_t Co) {
     char msg[320];

@@ -6,7 +6,7 @@
 The model treats the D slices of a volume as a batch of images; what makes it 3-d are two adapters per transformer block (before the
 attention and before the MLP) that mix every token with the same token of the neighbouring slices:
     x + up(gelu(conv_{3 x 1 x 1}(down(LayerNorm(x)))))
-with 384 adapter channels.  The depth convolution runs on token-major rows by ``training.functional.depth_conv3`` (csrc/depthconv.hip: an
+with 384 adapter channels.  The depth convolution runs on token-major rows by ``training.functional.depth_conv3`` (csrc/conv3d.hip: an
 implicit-shift MFMA GEMM, no im2col copy and no permute to channels-first); the two projections are ``functional.linear``.
 
 The forward pass is ONE taped composition in the style of ``training.encoders.image_encoder_forward`` - under autograd for training,

@@ -1227,5 +1227,5 @@ from ._labelprops import DistanceTargets, LabelProps, distance_targets, edt_squa
 from ._propagate import mask_box_prompts, mask_iou_counts, mask_logits, pack_bits, paint_max  # noqa: E402,F401  (csrc/propagate.hip)
 from ._embedpca import PCA_MAX_CHANNELS, PCA_MAX_COMPONENTS, PCA_MAX_UNITS, pca_moments, pca_moments_workspace_bytes, pca_project, pca_to_rgb  # noqa: E402,F401  (csrc/embedpca.hip; same arrangement)
 from ._semloss import SEMLOSS_MAX_CLASSES, SemanticLossStats, semantic_loss, semantic_loss_backward  # noqa: E402,F401  (csrc/semloss.hip; same arrangement)
-from ._depthconv import depth_conv3  # noqa: E402,F401  (csrc/depthconv.hip; same arrangement)
+from ._depthconv import depth_conv3  # noqa: E402,F401  (csrc/conv3d.hip's depth entry; same arrangement)
 from ._conv3d import column_sums, conv3d_k3, conv3d_k3_wgrad, instance_norm_apply, instance_norm_backward, instance_norm_stats  # noqa: E402,F401  (csrc/conv3d.hip; same arrangement)

@@ -195,7 +195,7 @@ def _mm_nt_cols(at: torch.Tensor, bt: torch.Tensor, ca: int, cb: int, k: int) ->
 
 
 class _DepthConv3(torch.autograd.Function):
-    """The 3-d adapter's ``Conv3d(Ci, Co, (3, 1, 1), padding="same")`` on token-major rows (csrc/depthconv.hip).  Forward: one
+    """The 3-d adapter's ``Conv3d(Ci, Co, (3, 1, 1), padding="same")`` on token-major rows (csrc/conv3d.hip).  Forward: one
     ``ops.cast_transpose`` of x (its bf16 copy, and X^T if the weight trains), then the kernel.  Backward: one ``ops.cast_transpose`` of
     dY (bf16 copy, dY^T, the column sums = the bias gradient), dX by the SAME kernel on W' (taps reversed, channels transposed), and
     dW per tap = dY^T shift_j(X) on the split-K product kernel over the rows whose tap lies inside the volume: the centre tap over all

@@ -1,4 +1,4 @@
-"""The depth convolution of the 3-d adapter (csrc/depthconv.hip, msam_depth_conv3_bf16) restated with torch's own operator:
+"""The depth convolution of the 3-d adapter (csrc/conv3d.hip, msam_depth_conv3_bf16) restated with torch's own operator:
 ``torch.nn.Conv3d(Ci, Co, (3, 1, 1), padding="same")`` in fp64 on operands rounded to bf16 - the arithmetic of the reference's
 ``NDBlockWrapper.adapter_conv`` - plus the case list and the error bounds of tests/test_depth_conv_host.py and
 tests/test_gpu_depth_conv.py.
@@ -41,6 +41,14 @@ def make_case(case, seed: int = 0):
     bias = (torch.randn(Co, generator=g, dtype=torch.float64) * 3).to(torch.float32).to(torch.float64)
     dy = r16(torch.randn(B * D, T, Co, generator=g, dtype=torch.float64) + off.flip(0)).reshape(B * D * T, Co)
     return x, w, bias, dy
+
+
+def embed_in_cube(w: torch.Tensor) -> torch.Tensor:
+    """[Co, Ci, 3, 1, 1] -> the 3 x 3 x 3 weight [Co, Ci, 3, 3, 3] that holds the depth taps at [:, :, kz, 1, 1] and zeros elsewhere: on a
+    volume [B, D, H = T, W = 1] it is the same convolution."""
+    cube = w.new_zeros(w.shape[0], w.shape[1], 3, 3, 3)
+    cube[:, :, :, 1, 1] = w[:, :, :, 0, 0]
+    return cube
 
 
 def to_volume(rows: torch.Tensor, B: int, D: int, T: int) -> torch.Tensor:

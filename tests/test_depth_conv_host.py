@@ -1,4 +1,4 @@
-"""msam_depth_conv3_bf16 (csrc/depthconv.hip) compiled for the host (tests/hip_host_shim.build_library) and driven through its C ABI on
+"""msam_depth_conv3_bf16 (csrc/conv3d.hip) compiled for the host (tests/hip_host_shim.build_library) and driven through its C ABI on
 the cases of tests/depth_conv_ref.py: every output element within the fp32 dot-product bound of torch's Conv3d in fp64, guard words around
 every buffer intact (the kernel forms no address outside its operands), bit-identical repeats, the input gradient through W' against
 the fp64 transpose convolution, and the refusals, which leave the output untouched."""
@@ -19,7 +19,7 @@ PATTERN = 0xA5
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    lib = build_library(str(tmp_path_factory.mktemp("host_depth_conv")), ROOT, files=["depthconv.hip"])
+    lib = build_library(str(tmp_path_factory.mktemp("host_depth_conv")), ROOT, files=["conv3d.hip"])
     lib.msam_depth_conv3_bf16.restype = C.c_int
     lib.msam_depth_conv3_bf16.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p]
     lib.emu_last_error.restype = C.c_char_p

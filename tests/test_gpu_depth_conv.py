@@ -1,4 +1,4 @@
-"""``ops.depth_conv3`` / ``training.functional.depth_conv3`` (csrc/depthconv.hip) on the device, on the cases and within the bounds of
+"""``ops.depth_conv3`` / ``training.functional.depth_conv3`` (csrc/conv3d.hip) on the device, on the cases and within the bounds of
 tests/depth_conv_ref.py: the forward pass and the input gradient through W' against torch's Conv3d in fp64 on the bf16-rounded operands,
 dX, dW and db of the autograd function against the fp64 autograd of the same restatement, and identical bits on a second run.  One more
 case (SPLIT_CASE) takes the weight gradient through the in-place split-K products, which the small cases are too short for."""

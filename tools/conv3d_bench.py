@@ -11,7 +11,8 @@ The five shapes are the first convolution of each of the four blocks and the hea
 
 Every figure is the median over ``--reps`` windows of at least ``--inner`` calls and at least ``--window-ms`` milliseconds each, between two
 device events, after ``--warmup`` calls of both forms (torch's convolution library searches its algorithms in the first call); the forms
-alternate window by window.  No ratio is fixed in advance: a stage where (a) is slower than (b) is printed as such.  The line "source"
+alternate window by window (tools/window_timer.py).  Before its timed windows a form runs a few sizing windows, which grow until one is
+measured to last ``--window-ms`` (at most 20000 calls; up to profiles/r10_simple_sam3d.md the size came from one 3-call window, capped at 500).  No ratio is fixed in advance: a stage where (a) is slower than (b) is printed as such.  The line "source"
 names the kernel sources the numbers belong to.
 
     python tools/conv3d_bench.py [--reps 7] [--inner 3] [--window-ms 200] [--warmup 3] [--depth 8] [--skip-decoder]
@@ -21,9 +22,10 @@ import json
 import os
 import sys
 
-import numpy as np
 import torch
 import torch.nn.functional as F
+
+import window_timer
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -32,35 +34,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 SHAPES = [(64, 256, 128), (128, 128, 64), (256, 64, 32), (512, 32, 16), (1024, 16, 8)]         # (side, Ci, Co)
 
 
-def _window(fn, inner):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(inner):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / inner                                    # ms per call
-
-
 def compare(forms, args):
-    """{name: callable} -> {name: {"ms", "ms_min_max"}} (a form that raises in its warm-up is reported under "failed")."""
-    times, failed = {k: [] for k in forms}, {}
-    for k, fn in list(forms.items()):
-        try:
-            for _ in range(args.warmup):
-                fn()
-            torch.cuda.synchronize()
-        except Exception as exc:
-            failed[k] = repr(exc)[:300]
-            del forms[k]
-    # a window lasts at least --window-ms: a few milliseconds would measure the clock and the scheduler as much as the kernels
-    inner = {k: max(args.inner, min(500, int(np.ceil(args.window_ms / _window(fn, args.inner))))) for k, fn in forms.items()}
-    for _ in range(args.reps):                                          # alternating: every form sees the same machine
-        for k, fn in forms.items():
-            times[k].append(_window(fn, inner[k]))
-    row = {k: {"ms": float(np.median(times[k])), "ms_min_max": [min(times[k]), max(times[k])], "calls_per_window": inner[k]} for k in forms}
-    if failed:
-        row["failed"] = failed
+    row = window_timer.compare(forms, args)
     if "a" in row and "b" in row:
         row["a_over_b"] = row["a"]["ms"] / row["b"]["ms"]
     return row
@@ -82,10 +57,7 @@ def torch_decoder(sd, x):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--inner", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--window-ms", type=float, default=200.0)
+    window_timer.add_arguments(ap)
     ap.add_argument("--depth", type=int, default=8)
     ap.add_argument("--classes", type=int, default=4)
     ap.add_argument("--skip-decoder", action="store_true")

@@ -1,27 +1,29 @@
 """Time of the 3-d adapter's depth convolution on the device (profiles/r09_sam3d.md), forward + backward (dX, dW, db), at the workload's
 shape B = 1, D = 8, T = 4096, Ci = Co = 384 (one adapter of vit_b on a volume of eight 1024 x 1024 slices), in three forms:
 
-  (a) ``training.functional.depth_conv3`` - csrc/depthconv.hip, the implicit-shift GEMM on token-major rows;
+  (a) ``training.functional.depth_conv3`` - csrc/conv3d.hip's tile body in its depth geometry, on token-major rows;
   (b) what the library could do before that kernel: ``torch.cat`` of the three shifted, zero-padded copies of x, [M, 3 Ci] fp32, and
       ``training.functional.linear`` on it;
   (c) ``F.conv3d`` on bf16 channels-first tensors, with the permute + cast to channels-first before it and the permute + cast back
       after it (what the reference's ``NDBlockWrapper`` does, under bf16 autocast).
 
-Every figure is the median over ``--reps`` windows of ``--inner`` calls each, between two device events, after ``--warmup`` calls; the
-forms alternate window by window.  "bytes": what each form's launches read and write, every operand counted once per launch that
+Every figure is the median over ``--reps`` windows of at least ``--inner`` calls and at least ``--window-ms`` milliseconds each, between two
+device events, after ``--warmup`` calls; the forms alternate window by window (tools/window_timer.py; profiles/r09_sam3d.md's figures came from
+fixed windows of 5 calls, about 2 ms each, and are not comparable).  "bytes": what each form's launches read and write, every operand counted once per launch that
 touches it, computed from the shapes below (``algorithm_bytes``) - not a counter reading.  The line "source" names the kernel sources
 the numbers belong to.
 
-    python tools/depth_conv_bench.py [--reps 10] [--inner 5] [--warmup 5] [--depth 8]
+    python tools/depth_conv_bench.py [--reps 7] [--inner 3] [--window-ms 200] [--warmup 3] [--depth 8]
 """
 import argparse
 import json
 import os
 import sys
 
-import numpy as np
 import torch
 import torch.nn.functional as F
+
+import window_timer
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -43,21 +45,9 @@ def algorithm_bytes(m: int, ci: int, co: int):
     return {"a": a, "b": b, "c": c}
 
 
-def _window(fn, inner):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(inner):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / inner                                    # ms per call
-
-
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--inner", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=5)
+    window_timer.add_arguments(ap)
     ap.add_argument("--depth", type=int, default=8)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -67,7 +57,7 @@ def main():
     B, D, S, Ci, Co = 1, args.depth, 64, 384, 384
     T, M = S * S, B * D * S * S
     print(json.dumps({"source": bench.csrc_sha16(), "device": torch.cuda.get_device_name(0), "reps": args.reps, "inner": args.inner,
-                      "warmup": args.warmup, "shape": {"B": B, "D": D, "T": T, "Ci": Ci, "Co": Co, "M": M}}), flush=True)
+                      "window_ms": args.window_ms, "warmup": args.warmup, "shape": {"B": B, "D": D, "T": T, "Ci": Ci, "Co": Co, "M": M}}), flush=True)
     g = torch.Generator().manual_seed(0)
     x = torch.randn(B * D, S, S, Ci, generator=g).cuda().requires_grad_()
     weight = torch.nn.Parameter((torch.randn(Co, Ci, 3, 1, 1, generator=g) * (3 * Ci) ** -0.5).cuda())
@@ -100,26 +90,13 @@ def main():
         finish("c", y.permute(0, 2, 3, 4, 1).float().contiguous().reshape(B * D, S, S, Co))
 
     forms = {"a": form_a, "b": form_b, "c": form_c}
-    times = {k: [] for k in forms}
-    failed = {}
-    for k, fn in list(forms.items()):
-        try:
-            for _ in range(args.warmup):
-                fn()
-            torch.cuda.synchronize()
-        except Exception as exc:                                        # (a library without this convolution: the other forms still count)
-            failed[k] = repr(exc)[:300]
-            del forms[k]
-    for _ in range(args.reps):                                          # alternating: every form sees the same machine
-        for k, fn in forms.items():
-            times[k].append(_window(fn, args.inner))
+    timed = window_timer.compare(forms, args)                           # (a library without this convolution: the other forms still count)
     nbytes = algorithm_bytes(M, Ci, Co)
     flops = 2.0 * M * 3 * Ci * Co * 3                                   # forward, dX, dW
-    row = {"flops_forward_backward": flops, "failed": failed}
+    row = {"flops_forward_backward": flops, "failed": timed.pop("failed", {})}
     for k in forms:
-        med = float(np.median(times[k]))
-        row[k] = {"ms": med, "ms_min_max": [min(times[k]), max(times[k])], "algorithm_bytes": nbytes[k],
-                  "bytes_per_s": nbytes[k] / (med * 1e-3), "flops_per_s": flops / (med * 1e-3)}
+        med = timed[k]["ms"]
+        row[k] = dict(timed[k], algorithm_bytes=nbytes[k], bytes_per_s=nbytes[k] / (med * 1e-3), flops_per_s=flops / (med * 1e-3))
     for k in forms:
         if k != "a":
             row[k]["ms_over_a"] = row[k]["ms"] / row["a"]["ms"]
