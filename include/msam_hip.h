@@ -462,6 +462,14 @@ typedef struct {
      * operands as hi + lo pairs of the 16-bit type (msam_*_split16): patch_w is then [D, 3*768] = [Whi | Whi | Wlo], neck0_w
      * [256, 3*D] and neck2_w [256, 3*2304] likewise (columns (ky,kx,c) within each block).  Same MFMA kernels, K widened. */
     int32_t split_io;
+    /* AdaptFormer (micro_sam/models/peft_sam.py AdaptFormer): a block whose adapter_wd entry is set adds
+     * norm2(x) + alpha * (relu(norm2(x) Wd^T + bd) Wu^T + bu) to the stream next to its MLP (msam_adapter_bf16).  adapter_wd 16-bit
+     * [adapter_dim, D], adapter_bd fp32 [adapter_dim], adapter_wu 16-bit [D, adapter_dim], adapter_bu fp32 [D], adapter_alpha fp32 [1]
+     * (device memory).  All NULL = no adapter.  Not together with fp8 (LN2's 16-bit output does not exist on that path). */
+    const void* adapter_wd[MSAM_MAX_BLOCKS]; const float* adapter_bd[MSAM_MAX_BLOCKS];
+    const void* adapter_wu[MSAM_MAX_BLOCKS]; const float* adapter_bu[MSAM_MAX_BLOCKS];
+    const float* adapter_alpha[MSAM_MAX_BLOCKS];
+    int32_t adapter_dim;
 } msam_encoder_t;
 
 int64_t msam_encoder_workspace_bytes(const msam_encoder_t* enc, int32_t B);
@@ -471,6 +479,16 @@ int64_t msam_encoder_workspace_bytes(const msam_encoder_t* enc, int32_t B);
 int msam_encoder_forward(const msam_encoder_t* enc, const float* img_f32, const uint8_t* img_u8, int32_t h, int32_t w,
                          int32_t B, float* out, void* workspace, int64_t workspace_bytes,
                          float* tap, int32_t tap_block, void* stream);
+
+/* The AdaptFormer branch of an encoder block in one launch (csrc/adapter.hip):
+ *     x[r, :] += y[r, :] + alpha * (relu(y[r, :] Wd^T + bd) Wu^T + bu)
+ * y16: 16-bit [R, D] rows of stride ldy (the block's norm2 output); wd16 16-bit [P, D]; bd fp32 [P]; wu16 16-bit [D, P]; bu fp32 [D];
+ * alpha fp32 [1] in DEVICE memory; x fp32 [R, D] rows of stride ldx, read and written.  fp32 accumulation; the hidden is rounded once to
+ * the 16-bit type and never leaves the chip.  Needs D % 128 == 0, P % 32 == 0 with 32 <= P <= 128, R >= 1, ldy >= D with ldy % 8 == 0,
+ * ldx >= D, y16 / wd16 / wu16 16-byte aligned, dtype16 MSAM_BF16 or MSAM_F16; anything else (and any null pointer) returns non-zero and
+ * launches nothing. */
+int msam_adapter_bf16(const void* y16, int64_t ldy, const void* wd16, const float* bd, const void* wu16, const float* bu,
+                      const float* alpha, float* x, int64_t ldx, int32_t R, int32_t D, int32_t P, int32_t dtype16, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Prompt encoder + mask decoder:  predictor.predict_torch(...)  up to the low-res logits

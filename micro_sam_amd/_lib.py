@@ -69,6 +69,8 @@ class EncoderParams(C.Structure):
         ("qkv_w8", _blk), ("qkv_cs", _blk), ("proj_w8", _blk), ("proj_cs", _blk),
         ("lin1_w8", _blk), ("lin1_cs", _blk), ("lin2_w8", _blk), ("lin2_cs", _blk),
         ("dtype16", _i32), ("split_io", _i32),
+        ("adapter_wd", _blk), ("adapter_bd", _blk), ("adapter_wu", _blk), ("adapter_bu", _blk), ("adapter_alpha", _blk),
+        ("adapter_dim", _i32),
     ]
 
 
@@ -283,6 +285,7 @@ _PROTOS = {
     "msam_instance_norm_backward": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _i64, _i32, _f32, _f32, _i32, _vp, _i64, _vp, _i64,
                                            _vp, _vp, _i64, _vp]),
     "msam_column_sums_f32": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp]),
+    "msam_adapter_bf16": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
 }
 OPTIONAL = set()
 

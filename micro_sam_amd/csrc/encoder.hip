@@ -78,6 +78,11 @@ extern "C" int msam_encoder_forward(const msam_encoder_t* enc, const float* img_
     const int dt = enc->dtype16 == MSAM_F16 ? MSAM_F16 : MSAM_BF16;        // the 16-bit type of every operand / stored activation
     if (fp8 && dt == MSAM_F16) { msam_set_error("msam_encoder_forward: fp8 projections go with the bf16 mode only"); return 1; }
     if (fp8 && (D % 128 || DA % 128)) { msam_set_error("msam_encoder_forward: fp8 needs embed_dim and heads * head_dim % 128 == 0"); return 1; }
+    for (int i = 0; i < enc->depth; ++i)
+        if (fp8 && (enc->adapter_wd[i] || enc->adapter_wu[i])) {
+            msam_set_error("msam_encoder_forward: AdaptFormer blocks do not go with fp8 (LN2 has no 16-bit output on that path)");
+            return 1;
+        }
     hipStream_t s = (hipStream_t)stream;
     EncWork w = carve(workspace, D, DA, B, enc->fp8, enc->split_io);
     const bool split = enc->split_io != 0;
@@ -153,6 +158,10 @@ extern "C" int msam_encoder_forward(const msam_encoder_t* enc, const float* img_
         CHECK(msam_layernorm(w.x, enc->ln2_w[i], enc->ln2_b[i], 1e-6f, R, D, w.xn, dt, 0, 0, s));
         CHECK(gemm(w.xn, D, enc->lin1_w[i], 4 * D, D, enc->lin1_b[i], w.hid, dt, 4 * D, MSAM_ACT_GELU, nullptr, 0, 0,
                    nullptr, 0, 0, 0));
+        // AdaptFormer: x += xn + alpha (relu(xn Wd^T + bd) Wu^T + bu), xn = norm2(x) still live between the two MLP products
+        if (enc->adapter_wd[i])
+            CHECK(msam_adapter_bf16(w.xn, D, enc->adapter_wd[i], enc->adapter_bd[i], enc->adapter_wu[i], enc->adapter_bu[i],
+                                    enc->adapter_alpha[i], w.x, D, R, D, enc->adapter_dim, dt, s));
         CHECK(gemm(w.hid, 4 * D, enc->lin2_w[i], D, 4 * D, enc->lin2_b[i], w.x, MSAM_F32, D, 0, w.x, MSAM_F32, D, nullptr, 0,
                    0, 0));
         }

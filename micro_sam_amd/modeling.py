@@ -247,6 +247,22 @@ class ImageEncoderViT(nn.Module):
             p.ln2_w[i], p.ln2_b[i] = k(_f32(blk.norm2.weight)), k(_f32(blk.norm2.bias))
             p.lin1_w[i], p.lin1_b[i] = k(_bf16(blk.mlp.lin1.weight)), k(_f32(blk.mlp.lin1.bias))
             p.lin2_w[i], p.lin2_b[i] = k(_bf16(blk.mlp.lin2.weight)), k(_f32(blk.mlp.lin2.bias))
+            if hasattr(blk.mlp, "down_proj"):          # models.peft_sam.AdaptFormer: the branch next to the MLP (msam_adapter_bf16)
+                if self.precision == "fp8":
+                    raise NotImplementedError("micro_sam_amd: AdaptFormer blocks do not run in the fp8 mode (LayerNorm 2 has no 16-bit "
+                                              "output on that path); use 'bf16', 'fp16', 'fp32' or 'split16'")
+                ad = blk.mlp
+                P = ad.down_proj.out_features
+                if p.adapter_dim not in (0, P):
+                    raise NotImplementedError("micro_sam_amd: the AdaptFormer blocks of one encoder must share their projection_size")
+                if P % 32 or not 32 <= P <= 128:
+                    raise NotImplementedError(f"micro_sam_amd: AdaptFormer projection_size {P} is not supported (a multiple of 32 in "
+                                              "32 .. 128)")
+                p.adapter_dim = P
+                p.adapter_wd[i], p.adapter_bd[i] = k(_bf16(ad.down_proj.weight)), k(_f32(ad.down_proj.bias))
+                p.adapter_wu[i], p.adapter_bu[i] = k(_bf16(ad.up_proj.weight)), k(_f32(ad.up_proj.bias))
+                alpha = ad.alpha if isinstance(ad.alpha, torch.Tensor) else torch.tensor([float(ad.alpha)])
+                p.adapter_alpha[i] = k(_f32(alpha).to(dev).reshape(1))       # a fixed number becomes a one-element device buffer
             if self.precision == "fp8":
                 from .ops import quant_weight_fp8
                 for name, wt in (("qkv", pad_rows(blk.attn.qkv.weight)), ("proj", pad_cols(blk.attn.proj.weight, H)),

@@ -29,7 +29,7 @@ from torch import nn
 
 from ..modeling import GRID, IMG_SIZE, PATCH, PROMPT_DIM
 from ..training import functional as HF
-from ..training.encoders import _attention, _mlp, _window_partition, _window_unpartition
+from ..training.encoders import _attention, _mlp, _norm, _window_partition, _window_unpartition
 
 _VIT = {"vit_b": (768, 12), "vit_l": (1024, 16), "vit_h": (1280, 16)}
 
@@ -170,7 +170,7 @@ class NDBlockWrapper(nn.Module):
         """x [B D, 64, 64, dim] -> the same shape: adapter, attention, adapter, MLP, each with its residual."""
         blk = self.block
         x = self._adapter(x, d_size, "")
-        y = HF.layer_norm(x, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps)
+        y = _norm(blk.norm1, x)
         if blk.window_size > 0:
             hw = y.shape[1:3]
             y, pad_hw = _window_partition(y, blk.window_size)
@@ -179,5 +179,5 @@ class NDBlockWrapper(nn.Module):
             y = _attention(blk.attn, y)
         x = x + y
         x = self._adapter(x, d_size, "_2")
-        y = HF.layer_norm(x, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
+        y = _norm(blk.norm2, x)
         return x + _mlp(blk.mlp, y)

@@ -1229,3 +1229,4 @@ from ._embedpca import PCA_MAX_CHANNELS, PCA_MAX_COMPONENTS, PCA_MAX_UNITS, pca_
 from ._semloss import SEMLOSS_MAX_CLASSES, SemanticLossStats, semantic_loss, semantic_loss_backward  # noqa: E402,F401  (csrc/semloss.hip; same arrangement)
 from ._depthconv import depth_conv3  # noqa: E402,F401  (csrc/conv3d.hip's depth entry; same arrangement)
 from ._conv3d import column_sums, conv3d_k3, conv3d_k3_wgrad, instance_norm_apply, instance_norm_backward, instance_norm_stats  # noqa: E402,F401  (csrc/conv3d.hip; same arrangement)
+from ._adapter import adapter_  # noqa: E402,F401  (csrc/adapter.hip; same arrangement)

@@ -8,7 +8,8 @@ SURVEY.md Appendix A; reference call sites ``micro_sam/util.py:674`` and ``micro
 tensor fp32, every product on the f32-input MFMA (``msam_strict_gemm``: exact fp32 products, fp32 accumulation), erf GELU, expf
 softmax, IEEE divisions (``csrc/strict.hip``).  What differs from torch's CPU result is the order of the additions inside a
 product.  Host code below only owns buffers and the sequence of library calls - there is no torch arithmetic on this path
-(``torch.cat`` / ``expand`` / views move data).
+(``torch.cat`` / ``expand`` / views move data), with one exception: an AdaptFormer block (``models.peft_sam.AdaptFormer``) adds its
+branch to the stream with one fp32 ``add_``.
 
 Cost: fp32 MFMA runs at 1/16 of the bf16 rate and nothing is folded: a 1024-prompt tile takes 58 ms against 5.8 ms on the default
 path (DESIGN.md sections 4 and 6 have the measured numbers and the steps that took it there from 116 ms); it is still 840 x the
@@ -317,6 +318,14 @@ class StrictEncoder:
                 ln2=(_f32(blk.norm2.weight, dev), _f32(blk.norm2.bias, dev), blk.norm2.eps),
                 lin1=(_f32(blk.mlp.lin1.weight, dev), _f32(blk.mlp.lin1.bias, dev)),
                 lin2=(_f32(blk.mlp.lin2.weight, dev), _f32(blk.mlp.lin2.bias, dev))))
+            if hasattr(blk.mlp, "down_proj"):
+                # models.peft_sam.AdaptFormer: alpha is folded into the up projection (weight preparation, fp32), so the branch is two
+                # products - ReLU, then the residual
+                ad = blk.mlp
+                alpha = ad.alpha.detach().to(device=dev, dtype=torch.float32) if isinstance(ad.alpha, torch.Tensor) else float(ad.alpha)
+                w["blocks"][-1]["adapter"] = ((_f32(ad.down_proj.weight, dev), _f32(ad.down_proj.bias, dev)),
+                                              ((_f32(ad.up_proj.weight, dev) * alpha).contiguous(),
+                                               (_f32(ad.up_proj.bias, dev) * alpha).contiguous()))
         nk = enc.neck
         w["neck0"] = _f32(nk[0].weight.reshape(PROMPT_DIM, D), dev)
         w["neck1"] = (_f32(nk[1].weight, dev), _f32(nk[1].bias, dev), nk[1].eps)
@@ -367,6 +376,14 @@ class StrictEncoder:
                 y = layer_norm(xs, *blk["ln2"], out=y)
                 hid = gemm(y, *blk["lin1"], act=ACT_GELU)
                 gemm(hid, *blk["lin2"], res=xs, out=xs)                                               # x + mlp(norm2(x))
+                if "adapter" in blk:
+                    # AdaptFormer: + y + alpha up(relu(down(y))), y = norm2(x) - two products (ReLU, then the residual onto y), and the
+                    # one fp32 add of this path that no product's epilogue can take (the stream already took the MLP's residual)
+                    down, up = blk["adapter"]
+                    ah = gemm(y, *down, act=ACT_RELU)
+                    gemm(ah, *up, res=y, out=y)
+                    xs.add_(y)
+                    del ah
                 del hid, att, y
             y = gemm(xs, w["neck0"])
             layer_norm(y, *w["neck1"], out=y)

@@ -38,13 +38,43 @@ def _rel_pos_table(rel_pos: torch.Tensor, size: int) -> torch.Tensor:
     return rel_pos[(idx[:, None] - idx[None, :]) + (size - 1)]
 
 
+def _is_ssf(mod) -> bool:
+    """``models.peft_sam.ScaleShiftLayer``: a wrapped layer with a per-channel ``scale`` and ``shift``."""
+    return hasattr(mod, "layer") and hasattr(mod, "scale") and hasattr(mod, "shift")
+
+
+def _linear(mod, x: torch.Tensor) -> torch.Tensor:
+    """``mod(x)`` for a linear layer; under SSF surgery the frozen layer, then ``* scale + shift`` as a separate step so that scale and
+    shift receive gradients (inference folds them into the weight and the bias)."""
+    if _is_ssf(mod):
+        return HF.linear(x, mod.layer.weight, mod.layer.bias) * mod.scale + mod.shift
+    return HF.linear(x, mod.weight, mod.bias)
+
+
+def _norm(mod, x: torch.Tensor) -> torch.Tensor:
+    """``mod(x)`` for a LayerNorm; under SSF surgery the wrapped norm, then ``* scale + shift``."""
+    if _is_ssf(mod):
+        return HF.layer_norm(x, mod.layer.weight, mod.layer.bias, mod.layer.eps) * mod.scale + mod.shift
+    return HF.layer_norm(x, mod.weight, mod.bias, mod.eps)
+
+
 def _qkv_projection(attn, x: torch.Tensor) -> torch.Tensor:
     """``attn.qkv(x)``; with LoRA surgery (``models.peft_sam.AttentionLoRA``, reference models/peft_sam.py:81-95) the frozen
     projection plus the low-rank branches ``alpha * B(A(x))`` on the q / k / v column blocks - the branches stay separate
-    products here so that A and B receive gradients (inference merges them into the weight)."""
+    products here so that A and B receive gradients (inference merges them into the weight).  FacT surgery
+    (``models.peft_sam.FacTSurgery``) likewise: the frozen projection plus ``FacTv(dropout(q_FacTs(FacTu(x))))`` on the q columns and
+    the same with ``v_FacTs`` on the v columns (the dropout modules act in training mode only); SSF: ``_linear``."""
     mod = attn.qkv
+    if hasattr(mod, "FacTu"):
+        out = HF.linear(x, mod.qkv_proj.weight, mod.qkv_proj.bias)
+        low = HF.linear(x, mod.FacTu.weight, None)
+        new_q, new_v = HF.linear(low, mod.q_FacTs.weight, None), HF.linear(low, mod.v_FacTs.weight, None)
+        if mod.dropout is not None:
+            new_q, new_v = mod.dp_q(new_q), mod.dp_v(new_v)
+        new_q, new_v = HF.linear(new_q, mod.FacTv.weight, None), HF.linear(new_v, mod.FacTv.weight, None)
+        return out + torch.cat([new_q, torch.zeros_like(new_q), new_v], dim=-1)
     if not hasattr(mod, "qkv_proj"):
-        return HF.linear(x, mod.weight, mod.bias)
+        return _linear(mod, x)
     out = HF.linear(x, mod.qkv_proj.weight, mod.qkv_proj.bias)
     branches = []
     for m in ("q", "k", "v"):
@@ -57,9 +87,16 @@ def _qkv_projection(attn, x: torch.Tensor) -> torch.Tensor:
 
 
 def _mlp(mlp, y: torch.Tensor) -> torch.Tensor:
-    """``MLPBlock.forward``; with ``MLPLoRA`` (reference models/peft_sam.py:127-131) both layers carry a low-rank branch."""
+    """``MLPBlock.forward``; with ``MLPLoRA`` (reference models/peft_sam.py:127-131) both layers carry a low-rank branch; with
+    ``AdaptFormer`` the module's whole forward, ``y + mlp_proj(y) + alpha * up_proj(dropout(relu(down_proj(y))))`` - its own residual
+    is its input ``y`` (the block adds ``x`` on top)."""
+    if hasattr(mlp, "mlp_proj"):
+        down = F.relu(HF.linear(y, mlp.down_proj.weight, mlp.down_proj.bias))
+        if mlp.dropout is not None:
+            down = mlp.dropout_layer(down)
+        return y + _mlp(mlp.mlp_proj, y) + mlp.alpha * HF.linear(down, mlp.up_proj.weight, mlp.up_proj.bias)
     if not hasattr(mlp, "mlp_layer"):
-        return HF.linear(F.gelu(HF.linear(y, mlp.lin1.weight, mlp.lin1.bias)), mlp.lin2.weight, mlp.lin2.bias)
+        return _linear(mlp.lin2, F.gelu(_linear(mlp.lin1, y)))
     base = mlp.mlp_layer
     h = HF.linear(y, base.lin1.weight, base.lin1.bias) + HF.linear(HF.linear(y, mlp.w_a_linear_1.weight, None), mlp.w_b_linear_1.weight, None)
     h = F.gelu(h)
@@ -79,7 +116,7 @@ def _attention(attn, x: torch.Tensor) -> torch.Tensor:
     bias_w = torch.einsum("bhwc,wkc->bhwk", r_q, _rel_pos_table(attn.rel_pos_w, S)).reshape(Bp * heads, N, S)
     o = HF.relpos_attention_auto(q, k, v, bias_h, bias_w, attn.scale)
     o = o.reshape(Bp, heads, S, S, hd).permute(0, 2, 3, 1, 4).reshape(Bp, S, S, C)
-    return HF.linear(o, attn.proj.weight, attn.proj.bias)
+    return _linear(attn.proj, o)
 
 
 def _window_partition(x: torch.Tensor, ws: int):
@@ -109,7 +146,7 @@ def image_encoder_forward(enc, x: torch.Tensor) -> torch.Tensor:
     x = HF.linear(patches, w.reshape(w.shape[0], -1), enc.patch_embed.proj.bias) + enc.pos_embed
     for blk in enc.blocks:
         shortcut = x
-        y = HF.layer_norm(x, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps)
+        y = _norm(blk.norm1, x)
         if blk.window_size > 0:
             H, W = y.shape[1:3]
             y, pad_hw = _window_partition(y, blk.window_size)
@@ -117,7 +154,7 @@ def image_encoder_forward(enc, x: torch.Tensor) -> torch.Tensor:
         else:
             y = _attention(blk.attn, y)
         x = shortcut + y
-        y = HF.layer_norm(x, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
+        y = _norm(blk.norm2, x)
         x = x + _mlp(blk.mlp, y)
     conv1, ln1, conv3, ln2 = enc.neck[0], enc.neck[1], enc.neck[2], enc.neck[3]
     y = HF.linear(x, conv1.weight.reshape(PROMPT_DIM, D), None)                         # 1 x 1 convolution

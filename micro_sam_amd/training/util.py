@@ -18,7 +18,8 @@ def get_trainable_sam_model(model_type: str = "vit_b", device=None, checkpoint_p
                             freeze: Optional[Union[str, List[str]]] = None, return_state: bool = False,
                             peft_kwargs: Optional[Dict] = None, flexible_load_checkpoint: bool = False, **model_kwargs):
     """Reference ``get_trainable_sam_model`` (training/util.py:77-151): the SAM of ``util.get_sam_model`` (checkpoint or the
-    ``state_dict=`` extension), optional LoRA surgery of the image encoder, the parts named in ``freeze`` (``image_encoder``,
+    ``state_dict=`` extension), optional PEFT surgery of the image encoder (``peft_kwargs``: any of the nine classes of
+    ``models.peft_sam``), the parts named in ``freeze`` (``image_encoder``,
     ``prompt_encoder``, ``mask_decoder``) set to ``requires_grad = False``, wrapped in ``TrainableSAM``.  By default nothing is
     frozen and the whole model trains."""
     from .. import util as msam_util

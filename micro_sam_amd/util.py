@@ -112,8 +112,9 @@ def get_sam_model(model_type: str = _DEFAULT_MODEL, device: Optional[Union[str, 
         raise ValueError("'micro-sam' does not support parameter efficient finetuning for 'mobile-sam'.")
     sam = modeling.sam_model_registry[abbreviated](**model_kwargs)
     if peft_kwargs and isinstance(peft_kwargs, dict):
-        # LoRA surgery of the image encoder before the weights are loaded (reference util.py:441-450); the low-rank
-        # updates are merged into the encoder's operand copies at inference (models/peft_sam.py)
+        # PEFT surgery of the image encoder before the weights are loaded (reference util.py:441-450); LoRA / FacT / SSF
+        # updates are merged into the encoder's operand copies at inference, an AdaptFormer branch runs as its own kernel
+        # (models/peft_sam.py)
         from .models import peft_sam
         peft_kwargs = dict(peft_kwargs)
         peft_kwargs.pop("quantize", None)
