@@ -247,6 +247,15 @@ int msam_upscale_fused_out(const void* keys, int32_t keys_blocked, int32_t P, co
                            const float* ln_w, const float* ln_b, float ln_eps, const void* w2, const float* b2,
                            const float* hyper, int32_t hyper_ld, int32_t mask0, int32_t nmask, void* low_res,
                            int32_t low_res_dtype, void* stream);
+/* the same, and the RANGE MAP of the low-res logits with them: range fp32 [P,nmask,256,4,2] = {min, max} of every 64-pixel
+ * segment (columns 64 seg .. 64 seg + 63) of every low-res row, taken from the values the kernel is about to store (exact, same
+ * bits as a reduction of low_res) - what msam_postprocess_masks_range reads first.  fp32 output only (low_res_dtype MSAM_F32);
+ * range == NULL is msam_upscale_fused_out.  Built into the shipped kernels: an error with "up_ln_two_pass", "up_gelu16" > 1
+ * or msam_upscale_set_prio(0) (those A/B kernels of the AMG path run with "amg_range_map" 0). */
+int msam_upscale_fused_range(const void* keys, int32_t keys_blocked, int32_t P, const void* w1, const float* b1,
+                             const float* ln_w, const float* ln_b, float ln_eps, const void* w2, const float* b2,
+                             const float* hyper, int32_t hyper_ld, int32_t mask0, int32_t nmask, void* low_res,
+                             int32_t low_res_dtype, float* range, void* stream);
 
 /* Live measurement of the GEMM kernel (the dominant kernel of the hot path) for bench.py's roofline leg:
  * after msam_profile_enable(1) every msam_gemm_bf16 launch is bracketed by HIP events on its stream;
@@ -263,8 +272,13 @@ int msam_fold_attn_set_dma(int32_t on);
  * "chain_variant" 9 the decoder passes the layer-0 probabilities and LayerNorm statistics from the attention kernel to the stream
  * kernel, msam_chain_handover_bytes of its workspace; 0 = the launches without it), "chain_handover_ring" (ring depth of the
  * hand-over stream kernel, 3 = default or 2), "up_gelu16" (1 = the up-scaling's GELUs in packed fp16 arithmetic, default in the fp16 decoder build;
- * 0 = packed fp32).  Returns 0, 1 for an unknown key. */
+ * 0 = packed fp32), "amg_range_map" (1 = default: the AMG path asks the decoder for the range map of its low-res logits and hands
+ * it to the post-processing; 0 = it does not: the launches of msam_upscale_fused_out and msam_postprocess_masks16.  The entry points
+ * below do what they are asked whatever its value: the caller that owns both ends reads it once per call, msam_tune_get).
+ * Returns 0, 1 for an unknown key. */
 int msam_tune_set(const char* key, int32_t value);
+/* the present value of "amg_range_map" (the one knob a caller decides on); 1 for any other key */
+int msam_tune_get(const char* key, int32_t* value);
 /* debug hook: phase timing of the folded image->token kernel (see csrc/decfold.hip, tools/i2t_timing.py) */
 int msam_debug_i2t_timing(int32_t enable, uint64_t* host_out);
 /* tuning / test hook: operand staging of the 256 x 256 tile kernel behind msam_gemm_bf16 (0 registers two tiles ahead,
@@ -530,6 +544,8 @@ typedef struct {
     int32_t up1_centred;             /* 1: up1_w / up1_b are CENTRED over the 64 output channels of every sub-pixel (rows sub*64 .. sub*64+63 of
                                       * up1_w minus their mean row, up1_b minus its mean) - LayerNorm2d's mean is then zero by construction and the
                                       * up-scaling kernel skips it (msam_upscale_fused_out, keys_blocked bit 1).  0: plain weights. */
+    float* low_res_range;            /* NULL, or fp32 [P,C,256,4,2]: the msam_decoder_forward_* calls also write the range map of `low_res`
+                                      * (msam_upscale_fused_range; fp32 low_res only, an error otherwise).  Set per call, like low_res_dtype. */
 } msam_decoder_t;
 
 /* Per-image constants of the decoder (dense positional encoding etc.): computed once per model. */
@@ -600,6 +616,17 @@ int msam_postprocess_masks(const float* low_res, int32_t N, int32_t in_h, int32_
 int msam_postprocess_masks16(const void* low_res, int32_t low_res_dtype, int32_t N, int32_t in_h, int32_t in_w, int32_t out_h,
                              int32_t out_w, float thr, float off, int32_t* counts, int32_t* boxes, uint32_t* bits, float* logits,
                              void* stream);
+/* msam_postprocess_masks16 on fp32 low-res logits without full-resolution logits, reading the RANGE MAP of msam_upscale_fused_range
+ * first: range fp32 [N,256,4,2].  In the x4 case (in = out = 1024 x 1024) every workgroup settles, from its slice of the map, the
+ * 32-row words whose whole low-res footprint clears thr, thr + off and thr - off by 0.01 on one side, writes them as constants and
+ * never loads their logits; the other words run msam_postprocess_masks16's code.  All outputs are identical to
+ * msam_postprocess_masks16's for finite logits.  The map may be loose (min lower, max higher): fewer words are settled; it must
+ * not be tighter than the logits (a stale or unwritten map gives wrong masks without an error).  A NaN entry leaves its words
+ * unsettled; NaN logits next to finite ones are dropped from a range, by msam_upscale_fused_range as by msam_postprocess_masks16's
+ * own per-word shortcut, and the two need not decide the same words then.  Any other size or a NULL map: msam_postprocess_masks16 itself. */
+int msam_postprocess_masks_range(const float* low_res, const float* range, int32_t N, int32_t in_h, int32_t in_w, int32_t out_h,
+                                 int32_t out_w, float thr, float off, int32_t* counts, int32_t* boxes, uint32_t* bits,
+                                 void* stream);
 /* uncrop_masks (reference micro_sam/instance_segmentation.py:250, segment_anything.utils.amg.uncrop_masks): place the
  * bit masks of a crop / tile, [N, ceil(crop_h/32), crop_w], at (x0, y0) of full-image bit masks [N, ceil(out_h/32), out_w]
  * (zero outside the crop).  N <= 65535. */

@@ -92,7 +92,7 @@ class DecoderParams(C.Structure):
         ("layer", TwoWayLayer * 2), ("final_attn", AttnW), ("nf_w", _vp), ("nf_b", _vp),
         ("up1_w", _vp), ("up1_b", _vp), ("up_ln_w", _vp), ("up_ln_b", _vp), ("up2_w", _vp), ("up2_b", _vp),
         ("hyp_w", (_vp * 3) * 4), ("hyp_b", (_vp * 3) * 4), ("iou_w", _vp * 3), ("iou_b", _vp * 3),
-        ("use_glds", _i32), ("low_res_dtype", _i32), ("up1_centred", _i32),
+        ("use_glds", _i32), ("low_res_dtype", _i32), ("up1_centred", _i32), ("low_res_range", _vp),
     ]
 
 
@@ -167,6 +167,7 @@ _PROTOS = {
     "msam_gemm_group_bf16": (_i32, [_vp, _i32, _vp]),
     "msam_fold_attn_set_dma": (_i32, [_i32]),
     "msam_tune_set": (_i32, [C.c_char_p, _i32]),
+    "msam_tune_get": (_i32, [C.c_char_p, C.POINTER(_i32)]),
     "msam_i2t_fold_operand_bytes": (_i64, [_i32]),
     "msam_i2t_fold_operands": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
     "msam_i2t0_t2i_workspace_bytes": (_i64, [_i32]),
@@ -189,6 +190,7 @@ _PROTOS = {
     "msam_chain_prepare_tables": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "msam_upscale_fused_layout": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "msam_upscale_fused_out": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp]),
+    "msam_upscale_fused_range": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
     "msam_upscale_set_prio": (_i32, [_i32]),
     "msam_layernorm_fp8": (_i32, [_vp, _vp, _vp, _f32, _i64, _i32, _vp, _vp, _vp]),
     "msam_quant_rows_fp8": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp]),
@@ -220,6 +222,7 @@ _PROTOS = {
                                     _i64, _vp]),
     "msam_postprocess_masks": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "msam_postprocess_masks16": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "msam_postprocess_masks_range": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "msam_rle_run_counts": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "msam_rle_encode": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "msam_mask_nms": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),
@@ -323,6 +326,13 @@ def load() -> C.CDLL:
         if lib.msam_tune_set(key.strip().encode(), int(val)) != 0:
             raise RuntimeError(f"micro_sam_amd: MSAM_TUNE: unknown knob {key!r}")
     return lib
+
+
+def tune_get(key: str) -> int:
+    """Present value of a knob the callers of the library decide on (``msam_tune_get``: "amg_range_map")."""
+    v = _i32(0)
+    check(load().msam_tune_get(key.encode(), C.byref(v)), "msam_tune_get")
+    return int(v.value)
 
 
 def decoder_dtype() -> torch.dtype:

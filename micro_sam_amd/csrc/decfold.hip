@@ -785,6 +785,9 @@ extern "C" int msam_fold_attn_set_dma(int32_t on) { g_fold_attn_dma = on; return
 //   "chain_handover"  1 (default) = with "chain_variant" 9 the attention kernel hands the layer-0 probabilities and LayerNorm statistics
 //                     to the stream kernel through the decoder workspace; 0 = the launches without the hand-over
 //   "chain_handover_ring" ring depth of the hand-over stream kernel: 3 (default) or 2
+//   "amg_range_map"   1 (default) = the AMG path asks the decoder for the range map of its low-res logits and hands it to the post-processing;
+//                     0 = it does not: the launches of msam_upscale_fused_out and msam_postprocess_masks16.  The library's entry points do not
+//                     read this knob - the caller that owns both ends does, once per call (msam_tune_get; predictor.py)
 extern int g_tune_i2t_wg_per_cu, g_tune_chain_variant, g_tune_chain_tmask, g_tune_up_gelu16, g_tune_up_ln_two_pass, g_tune_up_centred;
 void msam_gemm_set_dbg(int v);
 void msam_gemm_set_gw(int delay, int cls);
@@ -793,6 +796,7 @@ void msam_gemm_set_g3_epi(int v);
 extern int g_tune_tok_fuse;
 extern int g_tune_chain_handover, g_tune_chain_handover_ring;
 extern int g_tune_mlp_split_fused;
+extern int g_tune_amg_range_map;
 extern int g_tune_sgemm_bufs, g_tune_srel_mfma, g_tune_sgemm_small_below, g_tune_si2t_dbg, g_tune_si2t_late_us, g_tune_sattn_allh;
 int g_tune_dec_chain = 1, g_tune_dec_chain_min_p = 128;
 extern "C" int msam_tune_set(const char* key, int32_t value) {
@@ -807,6 +811,7 @@ extern "C" int msam_tune_set(const char* key, int32_t value) {
     else if (k == "up_gelu16") g_tune_up_gelu16 = value;
     else if (k == "up_ln_two_pass") g_tune_up_ln_two_pass = value;
     else if (k == "up_centred") g_tune_up_centred = value;
+    else if (k == "amg_range_map") g_tune_amg_range_map = value;
     else if (k == "gemm_dbg") msam_gemm_set_dbg(value);
     else if (k == "gw_delay") msam_gemm_set_gw(value, -1);
     else if (k == "gw_class") msam_gemm_set_gw(-2, value);
@@ -822,5 +827,12 @@ extern "C" int msam_tune_set(const char* key, int32_t value) {
     else if (k == "si2t_dbg") g_tune_si2t_dbg = value;
     else if (k == "si2t_late_us") g_tune_si2t_late_us = value;
     else { msam_set_error("msam_tune_set: unknown key"); return 1; }
+    return 0;
+}
+// the present value of a knob the callers of the library decide on ("amg_range_map"); 1 for any other key
+extern "C" int msam_tune_get(const char* key, int32_t* value) {
+    const std::string k = key ? key : "";
+    if (!value || k != "amg_range_map") { msam_set_error("msam_tune_get: unknown key"); return 1; }
+    *value = g_tune_amg_range_map;
     return 0;
 }

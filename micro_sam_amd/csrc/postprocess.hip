@@ -63,6 +63,140 @@ __global__ void finalize_boxes_kernel(int* __restrict__ boxes, int N) {
     }
 }
 
+// ---- the x4 path's parts, shared by postprocess_kernel and postprocess_range_kernel
+// The 10 x 66 low-res patch under a workgroup's 256 columns and one 32-row word is staged through LDS (one coalesced load of 660 floats
+// per word instead of 20 mostly redundant dword loads per thread): every thread carries up to three of its values from global memory
+// (x4_patch_load) into the LDS tile (x4_patch_store).
+struct X4Stage { int sr[3], sc[3]; float nx[3]; };
+MSAM_DEVINL void x4_stage_init(X4Stage& st, int cbase) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int idx = threadIdx.x + k * 256;
+        st.sr[k] = idx / 66; st.sc[k] = min(cbase + idx % 66, 255);
+        st.nx[k] = 0.f;
+    }
+}
+template <typename TL>
+MSAM_DEVINL void x4_patch_load(X4Stage& st, const TL* __restrict__ low, int yw) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if (threadIdx.x + k * 256 < 660) st.nx[k] = lowf(low[min(max(yw * 8 - 1 + st.sr[k], 0), 255) * 256 + st.sc[k]]);
+}
+MSAM_DEVINL void x4_patch_store(const X4Stage& st, float* tile) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if (threadIdx.x + k * 256 < 660) tile[threadIdx.x + k * 256] = st.nx[k];
+}
+// per-thread accumulators of a mask's statistics
+struct X4Acc { int c_hi, c_lo, c_m, ymin, ymax; bool any; };
+
+// One 32-row word of column x from the staged patch `tl`: the horizontal lerp of the 10 low-res rows under the word is shared by its 32
+// pixels (same arithmetic as stage1(), so still bit-exact): pixel b uses rows c, c+1 with c = (b + 2) / 4; vertical weights are
+// compile-time constants: frac(src) in {.625,.875,.125,.375} by b % 4 (exactly what axis_weights computes in fp32), except the two
+// clamped rows at the top of the image.
+template <bool LOGITS>
+MSAM_DEVINL void x4_word(const float* tl, const Axis& ax, int l0, int l1, int n, int x, int yw, int wpc, int out_h, int out_w, float thr, float hi_t,
+                         float lo_t, uint32_t* __restrict__ bits, float* __restrict__ logits, X4Acc& acc) {
+    const float W1[4] = {0.625f, 0.875f, 0.125f, 0.375f};
+    float t[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) t[k] = lerp_torch(ax.w0, tl[k * 66 + l0], ax.w1, tl[k * 66 + l1]);
+    const int nb = min(32, out_h - yw * 32);
+    // the three predicates v > thr, v > thr + off, v > thr - off are collected as sign bits of (t - v) (strictly
+    // negative <=> v > t; t - v == +0 for equality) shifted into three words: 2 instructions per predicate and
+    // pixel instead of compare + add-with-carry / select + or; pixel 0 ends up in bit 31 -> bit reverse
+    uint32_t wm = 0, wh = 0, wl = 0;
+    uint32_t word;
+    if (nb == 32) {
+        // full word (every word of a 1024-row mask).  Only the mask bits are needed per lane; the two stability
+        // counts are per-MASK totals, so each is one v_cmp into a scalar lane mask + a scalar popcount (SALU, a
+        // separate issue port) instead of a subtract + alignbit per pixel on the VALU: 6 instead of 8 VALU
+        // instructions per pixel in this VALU-bound loop (same comparisons: v > t  <=>  sign(t - v) set)
+        int s_hi = 0, s_lo = 0;
+        // Decided words: every pixel of the word is a convex combination of two of the ten t[k] (vertical weights
+        // w0 + w1 = 1 exactly), so it lies in [min t, max t] up to two fp32 roundings (< 0.003 for |t| < 8192).  If
+        // that interval clears all three thresholds by 0.01 on the same side the 32 comparisons are known without
+        // interpolating - for a real mask that is every word away from the object boundary.  The whole wave must be
+        // decided (ballot): otherwise the exact per-pixel path below runs for all of its lanes.
+        bool decided = false;
+        if (!LOGITS) {
+            const float tmin = fminf(fminf(fminf(t[0], t[1]), fminf(t[2], t[3])), fminf(fminf(t[4], t[5]), fminf(fminf(t[6], t[7]), fminf(t[8], t[9]))));
+            const float tmax = fmaxf(fmaxf(fmaxf(t[0], t[1]), fmaxf(t[2], t[3])), fmaxf(fmaxf(t[4], t[5]), fmaxf(fmaxf(t[6], t[7]), fmaxf(t[8], t[9]))));
+            const bool one = tmin > hi_t + 0.01f && tmax < 8192.f, zero = tmax < lo_t - 0.01f && tmin > -8192.f;
+            if (__ballot(!(one || zero)) == 0) {
+                decided = true;
+                word = one ? 0xffffffffu : 0u;
+                s_hi = s_lo = 32 * __popcll(__ballot(one));
+            }
+        }
+        if (!decided) {
+#pragma unroll
+            for (int b = 0; b < 32; ++b) {
+                float w1 = W1[b & 3];
+                if (b < 2 && yw == 0) w1 = 0.0f;
+                const float v = lerp_torch(1.0f - w1, t[(b + 2) / 4], w1, t[(b + 2) / 4 + 1]);
+                if (LOGITS) logits[((long)n * out_h + yw * 32 + b) * out_w + x] = v;
+                wm = __builtin_amdgcn_alignbit(wm, __float_as_uint(__fsub_rn(thr, v)), 31);
+                s_hi += __popcll(__ballot(v > hi_t));
+                s_lo += __popcll(__ballot(v > lo_t));
+            }
+            word = __brev(wm);
+        }
+        if ((threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) { acc.c_hi += s_hi; acc.c_lo += s_lo; }   // first active lane
+    } else {
+#pragma unroll
+        for (int b = 0; b < 32; ++b) {
+            float w1 = W1[b & 3];
+            if (b < 2 && yw == 0) w1 = 0.0f;
+            const float v = lerp_torch(1.0f - w1, t[(b + 2) / 4], w1, t[(b + 2) / 4 + 1]);
+            if (LOGITS) { if (b < nb) logits[((long)n * out_h + yw * 32 + b) * out_w + x] = v; }
+            wm = __builtin_amdgcn_alignbit(wm, __float_as_uint(__fsub_rn(thr, v)), 31);
+            wh = __builtin_amdgcn_alignbit(wh, __float_as_uint(__fsub_rn(hi_t, v)), 31);
+            wl = __builtin_amdgcn_alignbit(wl, __float_as_uint(__fsub_rn(lo_t, v)), 31);
+        }
+        const uint32_t valid = (1u << nb) - 1u;
+        word = __brev(wm) & valid;
+        acc.c_hi += __popc(__brev(wh) & valid); acc.c_lo += __popc(__brev(wl) & valid);
+    }
+    if (word) {
+        acc.c_m += __popc(word); acc.any = true;
+        acc.ymin = min(acc.ymin, yw * 32 + __ffs(word) - 1); acc.ymax = yw * 32 + 31 - __clz(word);
+    }
+    bits[((long)n * wpc + yw) * out_w + x] = word;
+}
+
+// a mask's statistics from its workgroups: wave reduction, then one set of atomics per workgroup
+MSAM_DEVINL void stats_reduce(int (*red)[7], int n, int x, int c_hi, int c_lo, int c_m, int ymin, int ymax, bool any, int* __restrict__ counts,
+                              int* __restrict__ boxes) {
+    int xmin = any ? x : 0x7fffffff, xmax = any ? x : -1;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        c_hi += __shfl_xor(c_hi, s); c_lo += __shfl_xor(c_lo, s); c_m += __shfl_xor(c_m, s);
+        ymin = min(ymin, __shfl_xor(ymin, s)); ymax = max(ymax, __shfl_xor(ymax, s));
+        xmin = min(xmin, __shfl_xor(xmin, s)); xmax = max(xmax, __shfl_xor(xmax, s));
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        red[wave][0] = c_hi; red[wave][1] = c_lo; red[wave][2] = c_m; red[wave][3] = xmin; red[wave][4] = ymin;
+        red[wave][5] = xmax; red[wave][6] = ymax;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int hi = 0, lo = 0, m = 0, x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = -1, y1 = -1;
+        for (int w = 0; w < 4; ++w) {
+            hi += red[w][0]; lo += red[w][1]; m += red[w][2];
+            x0 = min(x0, red[w][3]); y0 = min(y0, red[w][4]); x1 = max(x1, red[w][5]); y1 = max(y1, red[w][6]);
+        }
+        if (hi) atomicAdd(&counts[n * 3], hi);
+        if (lo) atomicAdd(&counts[n * 3 + 1], lo);
+        if (m) {
+            atomicAdd(&counts[n * 3 + 2], m);
+            atomicMin(&boxes[n * 4], x0); atomicMin(&boxes[n * 4 + 1], y0);
+            atomicMax(&boxes[n * 4 + 2], x1); atomicMax(&boxes[n * 4 + 3], y1);
+        }
+    }
+}
+
 // grid (ceil(out_w/256), N); thread = column x, loops over all 32-row words of its column (so a mask contributes
 // only ceil(W/256) x 7 atomics instead of one set per 32x256 patch - the atomics were the bottleneck)
 // LOGITS (store the up-sampled logits as well) is a compile-time switch: as a run-time test it put a scalar branch and
@@ -82,108 +216,23 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const TL* __restrict__
     int c_hi = 0, c_lo = 0, c_m = 0, ymin = 0x7fffffff, ymax = -1;
     bool any = false;
     if (!TWO_STAGE) {
-        // x4 fast path: the horizontal lerp of the 10 low-res rows under a 32-row word is shared by its 32 pixels
-        // (same arithmetic as stage1(), so still bit-exact): pixel b uses rows c, c+1 with c = (b + 2) / 4;
-        // vertical weights are compile-time constants: frac(src) in {.625,.875,.125,.375} by b % 4 (exactly what
-        // axis_weights computes in fp32), except the two clamped rows at the top of the image.
-        // The 10 x 66 low-res patch under the block's 256 columns is staged through LDS (one coalesced load of 660
-        // floats per word instead of 20 mostly redundant dword loads per thread), next word's patch in flight during
-        // the 32-row loop.
+        // x4 fast path (x4_word): the patch of the next word is in flight during the 32-row loop of this one
         const int cbase = max((int)blockIdx.x * 64 - 1, 0);
-        int sr[3], sc[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int idx = threadIdx.x + k * 256;
-            sr[k] = idx / 66; sc[k] = min(cbase + idx % 66, 255);
-        }
-        float nx[3] = {0.f, 0.f, 0.f};
-#define PP_LOAD(yw_)                                                                               \
-        _Pragma("unroll") for (int k = 0; k < 3; ++k)                                              \
-            if (threadIdx.x + k * 256 < 660) nx[k] = lowf(low[min(max((yw_) * 8 - 1 + sr[k], 0), 255) * 256 + sc[k]]);
-#define PP_STORE(buf_)                                                                             \
-        _Pragma("unroll") for (int k = 0; k < 3; ++k)                                              \
-            if (threadIdx.x + k * 256 < 660) tile[buf_][threadIdx.x + k * 256] = nx[k];
-        PP_LOAD(0);
-        PP_STORE(0);
+        X4Stage st;
+        x4_stage_init(st, cbase);
+        x4_patch_load(st, low, 0);
+        x4_patch_store(st, tile[0]);
         __syncthreads();
         const Axis ax = axis_weights(min(x, out_w - 1), 0.25f, 256);
         const int l0 = ax.i0 - cbase, l1 = ax.i1 - cbase;
-        const float W1[4] = {0.625f, 0.875f, 0.125f, 0.375f};
+        X4Acc acc = {0, 0, 0, 0x7fffffff, -1, false};
         for (int yw = 0; yw < wpc; ++yw) {
-            if (yw + 1 < wpc) { PP_LOAD(yw + 1); }
-            const float* tl = tile[yw & 1];
-            if (x < out_w) {
-                float t[10];
-#pragma unroll
-                for (int k = 0; k < 10; ++k) t[k] = lerp_torch(ax.w0, tl[k * 66 + l0], ax.w1, tl[k * 66 + l1]);
-                const int nb = min(32, out_h - yw * 32);
-                // the three predicates v > thr, v > thr + off, v > thr - off are collected as sign bits of (t - v) (strictly
-                // negative <=> v > t; t - v == +0 for equality) shifted into three words: 2 instructions per predicate and
-                // pixel instead of compare + add-with-carry / select + or; pixel 0 ends up in bit 31 -> bit reverse
-                uint32_t wm = 0, wh = 0, wl = 0;
-                uint32_t word;
-                if (nb == 32) {
-                    // full word (every word of a 1024-row mask).  Only the mask bits are needed per lane; the two stability
-                    // counts are per-MASK totals, so each is one v_cmp into a scalar lane mask + a scalar popcount (SALU, a
-                    // separate issue port) instead of a subtract + alignbit per pixel on the VALU: 6 instead of 8 VALU
-                    // instructions per pixel in this VALU-bound loop (same comparisons: v > t  <=>  sign(t - v) set)
-                    int s_hi = 0, s_lo = 0;
-                    // Decided words: every pixel of the word is a convex combination of two of the ten t[k] (vertical weights
-                    // w0 + w1 = 1 exactly), so it lies in [min t, max t] up to two fp32 roundings (< 0.003 for |t| < 8192).  If
-                    // that interval clears all three thresholds by 0.01 on the same side the 32 comparisons are known without
-                    // interpolating - for a real mask that is every word away from the object boundary.  The whole wave must be
-                    // decided (ballot): otherwise the exact per-pixel path below runs for all of its lanes.
-                    bool decided = false;
-                    if (!LOGITS) {
-                        const float tmin = fminf(fminf(fminf(t[0], t[1]), fminf(t[2], t[3])), fminf(fminf(t[4], t[5]), fminf(fminf(t[6], t[7]), fminf(t[8], t[9]))));
-                        const float tmax = fmaxf(fmaxf(fmaxf(t[0], t[1]), fmaxf(t[2], t[3])), fmaxf(fmaxf(t[4], t[5]), fmaxf(fmaxf(t[6], t[7]), fmaxf(t[8], t[9]))));
-                        const bool one = tmin > hi_t + 0.01f && tmax < 8192.f, zero = tmax < lo_t - 0.01f && tmin > -8192.f;
-                        if (__ballot(!(one || zero)) == 0) {
-                            decided = true;
-                            word = one ? 0xffffffffu : 0u;
-                            s_hi = s_lo = 32 * __popcll(__ballot(one));
-                        }
-                    }
-                    if (!decided) {
-#pragma unroll
-                        for (int b = 0; b < 32; ++b) {
-                            float w1 = W1[b & 3];
-                            if (b < 2 && yw == 0) w1 = 0.0f;
-                            const float v = lerp_torch(1.0f - w1, t[(b + 2) / 4], w1, t[(b + 2) / 4 + 1]);
-                            if (LOGITS) logits[((long)n * out_h + yw * 32 + b) * out_w + x] = v;
-                            wm = __builtin_amdgcn_alignbit(wm, __float_as_uint(__fsub_rn(thr, v)), 31);
-                            s_hi += __popcll(__ballot(v > hi_t));
-                            s_lo += __popcll(__ballot(v > lo_t));
-                        }
-                        word = __brev(wm);
-                    }
-                    if ((threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) { c_hi += s_hi; c_lo += s_lo; }   // first active lane
-                } else {
-#pragma unroll
-                    for (int b = 0; b < 32; ++b) {
-                        float w1 = W1[b & 3];
-                        if (b < 2 && yw == 0) w1 = 0.0f;
-                        const float v = lerp_torch(1.0f - w1, t[(b + 2) / 4], w1, t[(b + 2) / 4 + 1]);
-                        if (LOGITS) { if (b < nb) logits[((long)n * out_h + yw * 32 + b) * out_w + x] = v; }
-                        wm = __builtin_amdgcn_alignbit(wm, __float_as_uint(__fsub_rn(thr, v)), 31);
-                        wh = __builtin_amdgcn_alignbit(wh, __float_as_uint(__fsub_rn(hi_t, v)), 31);
-                        wl = __builtin_amdgcn_alignbit(wl, __float_as_uint(__fsub_rn(lo_t, v)), 31);
-                    }
-                    const uint32_t valid = (1u << nb) - 1u;
-                    word = __brev(wm) & valid;
-                    c_hi += __popc(__brev(wh) & valid); c_lo += __popc(__brev(wl) & valid);
-                }
-                if (word) {
-                    c_m += __popc(word); any = true;
-                    ymin = min(ymin, yw * 32 + __ffs(word) - 1); ymax = yw * 32 + 31 - __clz(word);
-                }
-                bits[((long)n * wpc + yw) * out_w + x] = word;
-            }
-            if (yw + 1 < wpc) { PP_STORE((yw + 1) & 1); }
+            if (yw + 1 < wpc) x4_patch_load(st, low, yw + 1);
+            if (x < out_w) x4_word<LOGITS>(tile[yw & 1], ax, l0, l1, n, x, yw, wpc, out_h, out_w, thr, hi_t, lo_t, bits, logits, acc);
+            if (yw + 1 < wpc) x4_patch_store(st, tile[(yw + 1) & 1]);
             __syncthreads();
         }
-#undef PP_LOAD
-#undef PP_STORE
+        c_hi = acc.c_hi; c_lo = acc.c_lo; c_m = acc.c_m; ymin = acc.ymin; ymax = acc.ymax; any = acc.any;
     } else {
         // (every lane of the wave walks the loop - the wave-wide vote below needs them all; lanes right of the image mirror the last
         //  column and neither count nor store)
@@ -284,33 +333,90 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const TL* __restrict__
             if (live) bits[((long)n * wpc + yw) * out_w + x] = word;
         }
     }
-    int xmin = any ? x : 0x7fffffff, xmax = any ? x : -1;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        c_hi += __shfl_xor(c_hi, s); c_lo += __shfl_xor(c_lo, s); c_m += __shfl_xor(c_m, s);
-        ymin = min(ymin, __shfl_xor(ymin, s)); ymax = max(ymax, __shfl_xor(ymax, s));
-        xmin = min(xmin, __shfl_xor(xmin, s)); xmax = max(xmax, __shfl_xor(xmax, s));
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[wave][0] = c_hi; red[wave][1] = c_lo; red[wave][2] = c_m; red[wave][3] = xmin; red[wave][4] = ymin;
-        red[wave][5] = xmax; red[wave][6] = ymax;
+    stats_reduce(red, n, x, c_hi, c_lo, c_m, ymin, ymax, any, counts, boxes);
+}
+
+// The x4 path at 1024 x 1024 without logits, reading the RANGE MAP of the low-res logits first (range [N][256 rows][4 segments of 64
+// columns][min, max], written by up_fused_kernel's output stage).  grid (4, N), thread = column, as postprocess_kernel.
+// A word's 10 x 66 footprint lies inside rows max(8 yw - 1, 0) .. min(8 yw + 8, 255) of the segments bx - 1 .. bx + 1 (clamped), so if the
+// range of THOSE clears the three thresholds by 0.01 on one side, every lane of the workgroup is in the "decided" case of x4_word with
+// the same constant word: the word is SETTLED - stored and counted as x4_word would, but its patch is neither loaded nor staged.  A
+// mask away from its object is settled altogether: 6 KB of map read instead of 256 KB of logits.  Unsettled words run x4_word.
+// (A map that is looser than the logits' true range - min lower, max higher - settles fewer words and changes no output.)
+// Non-finite logits: a NaN entry of the map leaves its words unsettled.  up_fused_kernel's map carries a NaN only where all four pixels of a lane are
+// NaN (its first step is a float min / max, which drops a NaN next to a number) - as x4_word's own decided test drops NaNs among a lane's ten values;
+// with NaN logits next to finite ones the two tests need not decide the same words.  Finite logits: identical outputs, always.
+__global__ __launch_bounds__(256) void postprocess_range_kernel(const float* __restrict__ low_res, const float* __restrict__ range, float thr,
+                                                                float off, int* __restrict__ counts, int* __restrict__ boxes,
+                                                                uint32_t* __restrict__ bits) {
+    __shared__ int red[4][7];
+    __shared__ float tile[2][10 * 66];
+    __shared__ float rmin[256], rmax[256];
+    __shared__ uint32_t settled[2];
+    const int bx = blockIdx.x, x = bx * 256 + threadIdx.x, n = blockIdx.y;
+    const float* low = low_res + (long)n * 65536;
+    const float hi_t = thr + off, lo_t = thr - off;
+    {
+        // low-res row threadIdx.x over the segments under and next to the workgroup's columns
+        const float* rr = range + ((long)n * 256 + threadIdx.x) * 8;
+        float a = 3.0e38f, b = -3.0e38f;
+        bool nan = false;                                // (fminf / fmaxf drop a NaN: a NaN entry of the map makes its row unsettled instead)
+        for (int s = max(bx - 1, 0); s <= min(bx + 1, 3); ++s) {
+            const float lo = rr[2 * s], hi = rr[2 * s + 1];
+            nan = nan || lo != lo || hi != hi;
+            a = fminf(a, lo); b = fmaxf(b, hi);
+        }
+        rmin[threadIdx.x] = nan ? -3.0e38f : a; rmax[threadIdx.x] = nan ? 3.0e38f : b;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        int hi = 0, lo = 0, m = 0, x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = -1, y1 = -1;
-        for (int w = 0; w < 4; ++w) {
-            hi += red[w][0]; lo += red[w][1]; m += red[w][2];
-            x0 = min(x0, red[w][3]); y0 = min(y0, red[w][4]); x1 = max(x1, red[w][5]); y1 = max(y1, red[w][6]);
-        }
-        if (hi) atomicAdd(&counts[n * 3], hi);
-        if (lo) atomicAdd(&counts[n * 3 + 1], lo);
-        if (m) {
-            atomicAdd(&counts[n * 3 + 2], m);
-            atomicMin(&boxes[n * 4], x0); atomicMin(&boxes[n * 4 + 1], y0);
-            atomicMax(&boxes[n * 4 + 2], x1); atomicMax(&boxes[n * 4 + 3], y1);
-        }
+    if (threadIdx.x < 64) {                              // (the whole first wave: lane yw < 32 judges word yw)
+        const int yw = threadIdx.x & 31;
+        float a = 3.0e38f, b = -3.0e38f;
+        for (int r = max(8 * yw - 1, 0); r <= min(8 * yw + 8, 255); ++r) { a = fminf(a, rmin[r]); b = fmaxf(b, rmax[r]); }
+        const bool lane = threadIdx.x < 32;
+        const bool one = lane && a > hi_t + 0.01f && b < 8192.f, zero = lane && b < lo_t - 0.01f && a > -8192.f;
+        const uint32_t m1 = (uint32_t)__ballot(one), m0 = (uint32_t)__ballot(zero);
+        if (threadIdx.x == 0) { settled[0] = m0; settled[1] = m1; }
     }
+    __syncthreads();
+    // bit yw: word yw is all ones / is settled - the same in every thread, and on the device in scalar registers (scalar branches below)
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t ones = (uint32_t)__builtin_amdgcn_readfirstlane((int)settled[1]), done = (uint32_t)__builtin_amdgcn_readfirstlane((int)settled[0]) | ones;
+#else
+    const uint32_t ones = settled[1], done = settled[0] | ones;
+#endif
+    const int cbase = max(bx * 64 - 1, 0);
+    X4Stage st;
+    x4_stage_init(st, cbase);
+    if (!(done & 1u)) {
+        x4_patch_load(st, low, 0);
+        x4_patch_store(st, tile[0]);
+        __syncthreads();
+    }
+    const Axis ax = axis_weights(x, 0.25f, 256);
+    const int l0 = ax.i0 - cbase, l1 = ax.i1 - cbase;
+    X4Acc acc = {0, 0, 0, 0x7fffffff, -1, false};
+    for (int yw = 0; yw < 32; ++yw) {
+        // the next word's patch is fetched and staged only if that word needs it (also behind a settled word)
+        const bool here = !((done >> yw) & 1u), next = yw + 1 < 32 && !((done >> (yw + 1)) & 1u);
+        if (next) x4_patch_load(st, low, yw + 1);
+        if (here) {
+            x4_word<false>(tile[yw & 1], ax, l0, l1, n, x, yw, 32, 1024, 1024, thr, hi_t, lo_t, bits, nullptr, acc);
+        } else {
+            uint32_t word = 0u;
+            if ((ones >> yw) & 1u) {
+                word = 0xffffffffu;
+                acc.c_hi += 32; acc.c_lo += 32; acc.c_m += 32; acc.any = true;
+                acc.ymin = min(acc.ymin, yw * 32); acc.ymax = yw * 32 + 31;
+            }
+            bits[((long)n * 32 + yw) * 1024 + x] = word;
+        }
+        if (next) x4_patch_store(st, tile[(yw + 1) & 1]);
+        // (the staged buffer must be complete before the next word reads it, and this word's readers done before the word after next
+        //  overwrites it: a barrier unless neither this word nor the next touches the tile.  `done` is the same in every thread.)
+        if (here || next) __syncthreads();
+    }
+    stats_reduce(red, n, x, acc.c_hi, acc.c_lo, acc.c_m, acc.ymin, acc.ymax, acc.any, counts, boxes);
 }
 
 // ---------------------------------------------------------------------------------------------- RLE
@@ -446,6 +552,22 @@ extern "C" int msam_postprocess_masks16(const void* low_res, int32_t low_res_dty
 #undef PP_LAUNCH
     hipLaunchKernelGGL(finalize_boxes_kernel, dim3((N + 255) / 256), dim3(256), 0, s, boxes, N);
     return msam_check_launch("msam_postprocess_masks");
+}
+
+int g_tune_amg_range_map = 1;            // msam_tune_set / msam_tune_get "amg_range_map": read by the CALLER that owns both ends (predictor.py asks for the map or not); the entry points do what they are asked
+
+extern "C" int msam_postprocess_masks_range(const float* low_res, const float* range, int32_t N, int32_t in_h, int32_t in_w, int32_t out_h,
+                                            int32_t out_w, float thr, float off, int32_t* counts, int32_t* boxes, uint32_t* bits,
+                                            void* stream) {
+    if (!range || in_h != 1024 || in_w != 1024 || out_h != 1024 || out_w != 1024)
+        return msam_postprocess_masks16(low_res, MSAM_F32, N, in_h, in_w, out_h, out_w, thr, off, counts, boxes, bits, nullptr, stream);
+    if (!low_res || !counts || !boxes || !bits || N <= 0) { msam_set_error("msam_postprocess_masks_range: null argument"); return 1; }
+    if (N > 65535) { msam_set_error("msam_postprocess_masks_range: at most 65535 masks per call"); return 1; }
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(init_stats_kernel, dim3((N + 255) / 256), dim3(256), 0, s, counts, boxes, N);
+    hipLaunchKernelGGL(postprocess_range_kernel, dim3(4, N), dim3(256), 0, s, low_res, range, thr, off, counts, boxes, bits);
+    hipLaunchKernelGGL(finalize_boxes_kernel, dim3((N + 255) / 256), dim3(256), 0, s, boxes, N);
+    return msam_check_launch("msam_postprocess_masks_range");
 }
 
 extern "C" int msam_postprocess_masks(const float* low_res, int32_t N, int32_t in_h, int32_t in_w, int32_t out_h,

@@ -43,7 +43,31 @@ struct UpArgs {
     int out16;
     int blocked;                         // keys in the blocked layout of decfold_tok.hip ([16-token tile][k-step][lane][8]) instead of row-major
     int centred;                         // w1 / b1 are centred over the 64 channels of every sub-pixel (see CEN)
+    float* range;                        // fp32 [P, nmask, 256, 4, 2]: {min, max} of every 64-pixel segment of every low-res row (CEN bit 1 only; else unused)
 };
+
+// min and max over the 16 lanes of a row, in every lane.  The values travel as order-preserving integer keys (fkey: the float's bits, the magnitude bits
+// of a negative one inverted - signed integer order is then the order of the floats; its own inverse), because the integer min / max take the lane
+// exchange as a DPP operand modifier of the instruction itself (v_min_i32_dpp: one instruction per step), while a float min of an exchanged value is
+// three (the exchange, a canonicalisation of its result, the min).  On the device the four steps are DPP row operations - no LDS crossbar, nothing on
+// the lgkm counter the kernel's hand-counted waits rely on; the host build exchanges with the same partners through __shfl_xor.  Same bits either way.
+MSAM_DEVINL int fkey(int i) { return i ^ ((i >> 31) & 0x7fffffff); }
+template <int CTRL, int XOR>
+MSAM_DEVINL int row_xchg(int v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, true);
+#else
+    return __shfl_xor(v, XOR);
+#endif
+}
+MSAM_DEVINL void row16_minmax(float& mnf, float& mxf) {
+    int mn = fkey((int)__float_as_uint(mnf)), mx = fkey((int)__float_as_uint(mxf));
+    mn = min(mn, row_xchg<0xB1, 1>(mn)); mx = max(mx, row_xchg<0xB1, 1>(mx));           // quad_perm [1, 0, 3, 2]
+    mn = min(mn, row_xchg<0x4E, 2>(mn)); mx = max(mx, row_xchg<0x4E, 2>(mx));           // quad_perm [2, 3, 0, 1]
+    mn = min(mn, row_xchg<0x141, 7>(mn)); mx = max(mx, row_xchg<0x141, 7>(mx));         // row_half_mirror: lane i of 8 <- lane 7 - i
+    mn = min(mn, row_xchg<0x140, 15>(mn)); mx = max(mx, row_xchg<0x140, 15>(mx));       // row_mirror: lane i of 16 <- lane 15 - i
+    mnf = __uint_as_float((uint32_t)fkey(mn)); mxf = __uint_as_float((uint32_t)fkey(mx));
+}
 
 // sum over the wave's four 16-lane rows, in every lane, without the LDS crossbar: v_permlane16_swap exchanges the odd rows of its first
 // operand with the even rows of its second (rows r0 r1 r2 r3 -> (r0 r0 r2 r2), (r1 r1 r3 r3)), v_permlane32_swap the same for 32-lane
@@ -159,8 +183,12 @@ MSAM_DEVINL void gelu_pk_h2(float x0, float x1, float x2, float x3, uint32_t& g0
 // msam_upscale_fused_out, `keys_blocked` bit 1) - the 64 channels of a (token, sub-pixel) then have mean zero by construction, LayerNorm2d's mean, its
 // exchange and the centring (16 + 6 + 8 vector instructions per tile and wave) are not computed and the variance is the plain mean of squares
 // (the two-pass value).  The other instantiations accept such weights too (they compute a mean of ~0).
+// CEN is a bit set: bit 0 = centred weights as above; bit 1 = the output stage also writes the range map `a.range` (fp32 output only): the {min, max} of
+// the 64-pixel segment of a low-res row that a 16-lane row of the wave is about to store - what the post-processing needs to settle a whole block of
+// 32-row words without reading the logits (postprocess.hip postprocess_range_kernel).  The logits are stored in full either way.
 template <int UF_PRIO, int G16, int LN2P = 0, int CEN = 0>
 __global__ __launch_bounds__(NTHR, 2) void up_fused_kernel(UpArgs a) {
+    constexpr bool CENW = (CEN & 1) != 0, RNG = (CEN & 2) != 0;
 #define UF_LDS_AHEAD 1
 #if defined(__HIP_DEVICE_COMPILE__) && UF_LDS_AHEAD
 #define UF_R16(dst_, base_, imm_) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst_) : "v"(base_), "n"(imm_))      // base_: LDS byte address (one VGPR), imm_: constant < 65536
@@ -309,6 +337,9 @@ __global__ __launch_bounds__(NTHR, 2) void up_fused_kernel(UpArgs a) {
     // output stage, one tile behind: every wave stores one patch row of all masks (lane >> 4 = mask, 4 pixels per lane: the same work in all four waves)
     // through buffer addressing - the per-thread part of the address is loop-invariant, and lanes of a mask >= nmask fall outside the descriptor's
     // range: the hardware drops their store (as it drops every lane's before the first tile: range 0)
+    // range map: the row's first lane stores {min, max} at [mask][row][segment] of the prompt (8 bytes; 32 per row, 8192 per mask); the other lanes' offset
+    // lies beyond any descriptor range, as that of a mask >= nmask does
+    const int rvoff = (lane & 15) == 0 ? ((lane >> 4) * 256 + w) * 32 : 0x40000000;
     float4 o4c = make_float4(0.f, 0.f, 0.f, 0.f);
     const char* obase_c = (const char*)a.out;
     uint32_t orange_c = 0;
@@ -324,6 +355,13 @@ __global__ __launch_bounds__(NTHR, 2) void up_fused_kernel(UpArgs a) {
         // 2^-11 relative, i.e. <= 5e-4 where the thresholds 0, +-1 are decided, against a logit error of ~3e-2)
         if (__builtin_amdgcn_readfirstlane(oesz) == 1) buf_store8(make_uint2(pack2h(o4c.x, o4c.y), pack2h(o4c.z, o4c.w)), ro, ovoff, oso);
         else buf_store16(make_uint4(__float_as_uint(o4c.x), __float_as_uint(o4c.y), __float_as_uint(o4c.z), __float_as_uint(o4c.w)), ro, ovoff, oso);
+        if constexpr (RNG) {
+            // (fp32 output: the map's base, range and tile offset are those of the logits / 32 - 8 bytes per 64 pixels of 4)
+            float mn = fminf(fminf(o4c.x, o4c.y), fminf(o4c.z, o4c.w)), mx = fmaxf(fmaxf(o4c.x, o4c.y), fmaxf(o4c.z, o4c.w));
+            row16_minmax(mn, mx);
+            const rsrc_t rr = make_rsrc((const char*)a.range + ((obu - (const char*)a.out) >> 5), (uint32_t)__builtin_amdgcn_readfirstlane((int)orange_c) >> 5);
+            buf_store8(make_uint2(__float_as_uint(mn), __float_as_uint(mx)), rr, rvoff, oso >> 5);
+        }
     };
     int q = 0, p = 0, key0 = 0;                                                        // compute cursor: tile number, prompt, first token of the tile
     const char* obase = (const char*)a.out;
@@ -410,16 +448,16 @@ __global__ __launch_bounds__(NTHR, 2) void up_fused_kernel(UpArgs a) {
         float s = 0.f, ss = 0.f;
 #pragma unroll
         for (int rt = 0; rt < 4; ++rt) {
-            if constexpr (!CEN) s += (uc[rt][0] + uc[rt][1]) + (uc[rt][2] + uc[rt][3]);
+            if constexpr (!CENW) s += (uc[rt][0] + uc[rt][1]) + (uc[rt][2] + uc[rt][3]);
 #pragma unroll
             for (int r = 0; r < 4; ++r) ss += uc[rt][r] * uc[rt][r];
         }
-        if constexpr (!CEN) s = wave_rows_sum(s);
+        if constexpr (!CENW) s = wave_rows_sum(s);
         ss = wave_rows_sum(ss);
         float mean = s * (1.f / 64.f);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (CEN) UF_S1(1, ss, 3); else UF_S1(1, mean, 3);      // in flight: kfb (1), kfa (2), g (0), b (0)  -> + kfb (3)
-        if constexpr (!CEN) {
+        if constexpr (CENW) UF_S1(1, ss, 3); else UF_S1(1, mean, 3);      // in flight: kfb (1), kfa (2), g (0), b (0)  -> + kfb (3)
+        if constexpr (!CENW) {
 #pragma unroll
             for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
@@ -438,7 +476,7 @@ __global__ __launch_bounds__(NTHR, 2) void up_fused_kernel(UpArgs a) {
             ss = wave_rows_sum(s2);
         }
         UF_S1(2, ss, 3);                                 // in flight: kfa (2), g (0), b (0), kfb (3)  -> + kfa (4)
-        float rstd = (LN2P || CEN) ? rsqrtf(ss * (1.f / 64.f) + a.eps) : rsqrtf(fmaxf(ss * (1.f / 64.f) - mean * mean, 0.f) + a.eps);
+        float rstd = (LN2P || CENW) ? rsqrtf(ss * (1.f / 64.f) + a.eps) : rsqrtf(fmaxf(ss * (1.f / 64.f) - mean * mean, 0.f) + a.eps);
         __builtin_amdgcn_sched_barrier(0);
         uint32_t g1w[4][2];
 #pragma unroll
@@ -575,8 +613,16 @@ extern "C" int msam_upscale_fused_out(const void* keys, int32_t keys_blocked, in
                                       const float* ln_w, const float* ln_b, float ln_eps, const void* w2, const float* b2,
                                       const float* hyper, int32_t hyper_ld, int32_t mask0, int32_t nmask, void* low_res,
                                       int32_t low_res_dtype, void* stream) {
+    return msam_upscale_fused_range(keys, keys_blocked, P, w1, b1, ln_w, ln_b, ln_eps, w2, b2, hyper, hyper_ld, mask0, nmask, low_res, low_res_dtype,
+                                    nullptr, stream);
+}
+
+extern "C" int msam_upscale_fused_range(const void* keys, int32_t keys_blocked, int32_t P, const void* w1, const float* b1,
+                                        const float* ln_w, const float* ln_b, float ln_eps, const void* w2, const float* b2,
+                                        const float* hyper, int32_t hyper_ld, int32_t mask0, int32_t nmask, void* low_res,
+                                        int32_t low_res_dtype, float* range, void* stream) {
     if (low_res_dtype != MSAM_F32 && low_res_dtype != MSAM_F16) {
-        msam_set_error("msam_upscale_fused_out: low_res_dtype is MSAM_F32 or MSAM_F16");
+        msam_set_error("msam_upscale_fused_out / _range: low_res_dtype is MSAM_F32 or MSAM_F16");
         return 1;
     }
     if (!keys || !w1 || !b1 || !ln_w || !ln_b || !w2 || !b2 || !hyper || !low_res || P <= 0) {
@@ -585,6 +631,12 @@ extern "C" int msam_upscale_fused_out(const void* keys, int32_t keys_blocked, in
     }
     if (nmask < 1 || nmask > 3 || mask0 < 0 || mask0 + nmask > 4 || hyper_ld < 32 || hyper_ld % 4) {
         msam_set_error("msam_upscale_fused: 1 <= nmask <= 3 masks out of 4, hyper_ld >= 32 and a multiple of 4");
+        return 1;
+    }
+    if (range && low_res_dtype != MSAM_F32) { msam_set_error("msam_upscale_fused_range: the range map goes with fp32 low-res logits only"); return 1; }
+    // the range map is built into the shipped instantiations only (there is no quiet launch without it)
+    if (range && (!g_uf_prio || g_tune_up_ln_two_pass || (MSAM_DEC_F16 && g_tune_up_gelu16 > 1))) {
+        msam_set_error("msam_upscale_fused_range: no range map with the up_ln_two_pass / up_gelu16 > 1 / priority 0 kernels");
         return 1;
     }
     UpArgs a{};
@@ -596,11 +648,24 @@ extern "C" int msam_upscale_fused_out(const void* keys, int32_t keys_blocked, in
     int ks = 1;
     while (P * ks < 2 * cus && ks < 16) ks *= 2;
     a.KS = ks; a.nitems = P * ks; a.out = low_res; a.out16 = low_res_dtype == MSAM_F16; a.blocked = keys_blocked & 1; a.centred = (keys_blocked >> 1) & 1;
+    a.range = range;
     const int grid = a.nitems < 2 * cus ? a.nitems : 2 * cus;
     const double rows = (double)P * T;
     const double flops = rows * (2.0 * 256 * 256 + 4 * 2.0 * 128 * 64 + 16 * 3 * 2.0 * 16 * 32);
-    const double bytes = rows * C * 2 + (double)P * nmask * 256 * 256 * (low_res_dtype == MSAM_F16 ? 2 : 4);
+    const double bytes = rows * C * 2 + (double)P * nmask * 256 * 256 * (low_res_dtype == MSAM_F16 ? 2 : 4) + (range ? (double)P * nmask * 256 * 4 * 8 : 0.0);
     msam_profile_mark2(stream, 1, flops, bytes, 4);
+    // the kernel's fourth template argument (CEN) is a bit set: 1 = centred weights, 2 = write the range map - hence 3 and 2 with a map, 1 and 0 without
+    const bool cen = a.centred && g_tune_up_centred;
+#if MSAM_DEC_F16
+    if (range && g_tune_up_gelu16) {
+        if (cen) hipLaunchKernelGGL((up_fused_kernel<1, 1, 0, 3>), dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((up_fused_kernel<1, 1, 0, 2>), dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, a);
+    } else
+#endif
+    if (range) {
+        if (cen) hipLaunchKernelGGL((up_fused_kernel<1, 0, 0, 3>), dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((up_fused_kernel<1, 0, 0, 2>), dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, a);
+    } else
 #if MSAM_DEC_F16
     if (g_tune_up_gelu16 == 2) hipLaunchKernelGGL((up_fused_kernel<1, 2>), dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, a);
     else if (g_tune_up_gelu16 == 3) hipLaunchKernelGGL((up_fused_kernel<1, 3>), dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, a);

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import List, Optional, Tuple
+from typing import List, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -762,6 +762,7 @@ class Sam(nn.Module):
         iou = torch.empty((P, nc), dtype=torch.float32, device=dev)
         ws = self._workspace(P)
         p.low_res_dtype = _lib.F32
+        p.low_res_range = None
         _lib.check(_lib.load().msam_decoder_forward_embeddings(
             C.byref(p), consts.data_ptr(), state.data_ptr(), sp.data_ptr() if Ns > 0 else None, Ns, dptr, eptr, P,
             1 if multimask_output else 0, low.data_ptr(), iou.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
@@ -771,12 +772,20 @@ class Sam(nn.Module):
     @torch.no_grad()
     def decode(self, features: torch.Tensor, point_coords: Optional[torch.Tensor], point_labels: Optional[torch.Tensor],
                boxes: Optional[torch.Tensor] = None, mask_input: Optional[torch.Tensor] = None,
-               multimask_output: bool = True, low_res_dtype: torch.dtype = torch.float32) -> Tuple[torch.Tensor, torch.Tensor]:
+               multimask_output: bool = True, low_res_dtype: torch.dtype = torch.float32,
+               range_map: Union[bool, torch.Tensor] = False) -> Tuple[torch.Tensor, ...]:
         """prompt_encoder + mask_decoder of ``SamPredictor.predict_torch`` for one image embedding [1,256,64,64].
 
         point_coords [P,Np,2] / boxes [P,4] are in the 1024 input frame.  Returns (low_res [P,C,256,256], iou [P,C]).
         ``low_res_dtype=torch.float16``: the low-res logits leave the up-scaling kernel as fp16 (the AMG path: 3072 masks per tile
-        are handed to the fused post-processing and never returned - half the HBM round trip; ``predict_torch`` keeps fp32)."""
+        are handed to the fused post-processing and never returned - half the HBM round trip; ``predict_torch`` keeps fp32).
+        ``range_map`` (fp32 logits of the kernel path, no mask prompt): True, or a float32 device tensor [P,C,256,4,2] to fill - the
+        up-scaling kernel also writes the {min, max} of every 64-pixel segment of every low-res row, and the map is returned as a
+        third value (``ops.postprocess_masks(range_map=...)`` reads it first).  The map is written whenever it is asked for; whether to
+        ask is the caller's decision (``SamPredictor.predict_masks_device`` reads ``msam_tune_set("amg_range_map", ...)`` for it)."""
+        want_range = range_map is not False and range_map is not None
+        if want_range and (low_res_dtype != torch.float32 or self.reference_formulation or mask_input is not None):
+            raise ValueError("range_map goes with float32 low-res logits of the kernel path, without a mask prompt")
         if low_res_dtype not in (torch.float32, torch.float16):
             raise ValueError("low_res_dtype is torch.float32 or torch.float16")
         if features.numel() != PROMPT_DIM * GRID * GRID:
@@ -810,6 +819,12 @@ class Sam(nn.Module):
         low = torch.empty((P, nc, 256, 256), dtype=low_res_dtype, device=dev)
         iou = torch.empty((P, nc), dtype=torch.float32, device=dev)
         p.low_res_dtype = _lib.F16 if low_res_dtype == torch.float16 else _lib.F32      # (read by this call only: set per call)
+        rng = None
+        if want_range:
+            rng = range_map if isinstance(range_map, torch.Tensor) else torch.empty((P, nc, 256, 4, 2), dtype=torch.float32, device=dev)
+            if rng.dtype != torch.float32 or tuple(rng.shape) != (P, nc, 256, 4, 2) or not rng.is_contiguous() or rng.device != low.device:
+                raise ValueError(f"range_map must be a contiguous float32 tensor [{P},{nc},256,4,2] on {low.device}")
+        p.low_res_range = _lib.ptr(rng)                                                  # (likewise)
         need = lib.msam_decoder_workspace_bytes(P)
         if self._dec_ws is None or self._dec_ws.numel() < need or self._dec_ws.device != dev:
             self._dec_ws = None
@@ -823,6 +838,8 @@ class Sam(nn.Module):
             C.byref(p), C.byref(self._mask_params), consts.data_ptr(), state.data_ptr(), _lib.ptr(pts), _lib.ptr(lbl), Np,
             _lib.ptr(bx), _lib.ptr(msk), P, 1 if multimask_output else 0, low.data_ptr(), iou.data_ptr(),
             self._dec_ws.data_ptr(), self._dec_ws.numel(), _lib.stream_ptr()), "msam_decoder_forward")
+        if want_range:
+            return low, iou, rng
         return low, iou
 
 

@@ -400,8 +400,12 @@ def global_attention(q, k, v, rel_h, rel_w, scale: Optional[float] = None) -> to
 
 def postprocess_masks(low_res: torch.Tensor, input_size: Tuple[int, int], original_size: Tuple[int, int],
                       mask_threshold: float = 0.0, stability_offset: float = 1.0,
-                      want_logits: bool = False) -> Dict[str, torch.Tensor]:
+                      want_logits: bool = False, range_map: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """Fused Sam.postprocess_masks + stability counts + threshold + boxes + bit packing for masks [N,256,256].
+
+    ``range_map`` (float32 [N,256,4,2], with float32 ``low_res`` and without logits): the {min, max} of every 64-pixel segment of every
+    low-res row, as ``Sam.decode(range_map=True)`` returns it - read first, so that words away from a mask's boundary are written
+    without reading their logits (msam_postprocess_masks_range; same outputs).
 
     Returns dict(counts int32 [N,3] = (#>thr+off, #>thr-off, #>thr), boxes int32 [N,4] xyxy, bits uint32
     [N, ceil(H/32), W] as int32 storage, logits fp32 [N,H,W] when requested)."""
@@ -417,10 +421,19 @@ def postprocess_masks(low_res: torch.Tensor, input_size: Tuple[int, int], origin
     boxes = torch.empty((N, 4), dtype=torch.int32, device=dev)
     bits = torch.empty((N, (H + 31) // 32, W), dtype=torch.int32, device=dev)
     logits = torch.empty((N, H, W), dtype=torch.float32, device=dev) if want_logits else None
+    if range_map is not None:
+        _need(low_res.dtype == torch.float32 and not want_logits, "range_map goes with float32 low_res and want_logits=False")
+        _t("range_map", range_map, _F32, (N, 256, 4, 2), dev)
     lib = _lib.load()
     step = 65535
     for s in range(0, N, step):
         n = min(step, N - s)
+        if range_map is not None:
+            _lib.check(lib.msam_postprocess_masks_range(
+                low_res[s:].data_ptr(), range_map[s:].data_ptr(), n, int(input_size[0]), int(input_size[1]), H, W, float(mask_threshold),
+                float(stability_offset), counts[s:].data_ptr(), boxes[s:].data_ptr(), bits[s:].data_ptr(), _lib.stream_ptr()),
+                "msam_postprocess_masks_range")
+            continue
         _lib.check(lib.msam_postprocess_masks16(
             low_res[s:].data_ptr(), low_dt, n, int(input_size[0]), int(input_size[1]), H, W, float(mask_threshold),
             float(stability_offset), counts[s:].data_ptr(), boxes[s:].data_ptr(), bits[s:].data_ptr(),

@@ -116,11 +116,21 @@ class SamPredictor:
         Returns (iou [B,C], dict(counts, boxes, bits)) - see ops.postprocess_masks."""
         if not self.is_image_set:
             raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
-        # the low-res logits go from the up-scaling kernel to the post-processing kernel as fp16 (never returned to the caller)
-        low, iou = self.model.decode(self.features, point_coords, point_labels, boxes, None, multimask_output,
-                                     low_res_dtype=self.model.amg_low_res_dtype)
+        # the low-res logits go from the up-scaling kernel to the post-processing kernel (never returned to the caller).  fp32 logits of a
+        # 1024 x 1024 tile come with their range map: the post-processing settles every block of words away from the mask's boundary
+        # from it and reads the logits of the others only.  The knob is read HERE, once for both ends (msam_tune_set("amg_range_map", 0):
+        # no map is asked for - the launches without it, which the up-scaling kernel's A/B variants up_ln_two_pass / up_gelu16 > 1 need)
+        from . import _lib
+        dt = self.model.amg_low_res_dtype
+        with_map = (dt == torch.float32 and not self.model.reference_formulation
+                    and tuple(int(v) for v in self.input_size) == (1024, 1024)
+                    and tuple(int(v) for v in self.original_size) == (1024, 1024) and _lib.tune_get("amg_range_map") == 1)
+        out = self.model.decode(self.features, point_coords, point_labels, boxes, None, multimask_output, low_res_dtype=dt,
+                                range_map=with_map)
+        low, iou = out[0], out[1]
         from .ops import postprocess_masks
         b, c = low.shape[:2]
         res = postprocess_masks(low.reshape(b * c, 256, 256), self.input_size, self.original_size,
-                                self.model.mask_threshold, stability_score_offset, want_logits=False)
+                                self.model.mask_threshold, stability_score_offset, want_logits=False,
+                                range_map=out[2].reshape(b * c, 256, 4, 2) if with_map else None)
         return iou, res
