@@ -987,6 +987,33 @@ int msam_paint_max(const uint32_t* bits, const int32_t* ids, const uint8_t* keep
                    void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Cross-tile mask NMS and label merge of tile-local records (util.apply_nms on records with a global_bbox; reference
+ * micro_sam/util.py:1698-1747 _calculate_tiled_mask_overlap_matrix, :1773-1848 mask_data_to_segmentation; csrc/tilemerge.hip).
+ * Both entry points read a RECORD TABLE in device memory:
+ *   words       : uint32, flat - the bit masks of all tiles one after the other, each [n, ceil(th / 32), tw] as msam_mask_pack writes
+ *                 them (bit b of word row yw = row yw * 32 + b, tail bits zero);
+ *   word_offset : int64 [K], a record's first word;
+ *   geom        : int32 [K, 8] = wpc, tw (words per column and width of the record's tile), bx, by, bw, bh (its bbox, xywh in the tile),
+ *                 gx, gy (the first two entries of its global_bbox).
+ * Tiles may differ in shape and lie at any offset from each other.  The caller guarantees that every record's words lie inside
+ * `words`; beyond that a word is read only where 0 <= word row < wpc and 0 <= x < tw (zero elsewhere) and a label is written only
+ * inside [H, W], so a malformed table cannot fault.  Integer sums and integer atomics: two runs give the same bits.  Kernels on
+ * `stream`, no workspace, no synchronisation.
+ * ------------------------------------------------------------------------------------------------- */
+/* inter[p] = number of pixels set in both masks of pair p = (i, j) (pairs: int32 [Np, 2], record indices in [0, K); others give 0)
+ * inside the intersection window of their global xywh boxes, [max(gx_i, gx_j), min(gx_i + bw_i, gx_j + bw_j)) x the same in y, each mask
+ * read at the window's coordinates minus its tile origin (gx - bx, gy - by).  bw / bh are max - min of the inclusive box as in the
+ * reference, so an object's last row and column lie outside the window; an empty window gives 0.  One launch over the Np pairs. */
+int msam_tiled_mask_overlaps(const uint32_t* words, const int64_t* word_offset, const int32_t* geom, int32_t K, const int32_t* pairs,
+                             int32_t Np, int32_t* inter, void* stream);
+/* The paint step of mask_data_to_segmentation(..., merge_exclusively=True) for records with a global_bbox: label (int32 [H, W], zeroed
+ * here) = M - r at pixel (gy + dy, gx + dx), dy < bh, dx < bw, for the FIRST r whose record order[r] (int32 [M], record indices; a
+ * negative entry paints nothing) has its mask bit (by + dy, bx + dx) set.  Distinct values per record, larger = earlier: an integer
+ * atomicMax, the same image on every run.  A memset and one launch. */
+int msam_paint_tiled(const uint32_t* words, const int64_t* word_offset, const int32_t* geom, const int32_t* order, int32_t M, int32_t H,
+                     int32_t W, int32_t* label, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * PCA projection of image embeddings for visualization (micro_sam/visualization.py compute_pca, i.e. elf's embedding_pca on sklearn's
  * PCA; csrc/embedpca.hip).  A call works on U units; a unit is one embedding in its own channel-major layout, float32 [C, N] with
  * N = H * W positions.  1 <= U <= 65535, 1 <= C <= 256, N >= 1, C * N < 2^31.  The eigen-decomposition of the [C, C] matrix is the

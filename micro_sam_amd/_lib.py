@@ -289,6 +289,8 @@ _PROTOS = {
                                            _vp, _vp, _i64, _vp]),
     "msam_column_sums_f32": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp]),
     "msam_adapter_bf16": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "msam_tiled_mask_overlaps": (_i32, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp]),
+    "msam_paint_tiled": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
 }
 OPTIONAL = set()
 

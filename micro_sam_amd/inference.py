@@ -303,5 +303,29 @@ def batched_tiled_inference(predictor: SamPredictor, image: Optional[np.ndarray]
     if optimize_memory:
         return _stitch_segmentation(masks, tile_ids, tiling, halo, output_shape=shape)
     if return_instance_segmentation:
-        masks = util.mask_data_to_segmentation(masks, shape=shape, min_object_size=0)
+        masks = _merge_tiled_records(masks, shape)
     return masks
+
+
+def _merge_tiled_records(masks, shape) -> np.ndarray:
+    """``util.mask_data_to_segmentation(masks, shape=shape, min_object_size=0)`` for the tile-local records above.  Their masks are
+    dense device tensors: they are packed and painted through their global boxes where they are (csrc/tilemerge.hip) and the label
+    image comes to the host once.  Every record paints its own ``seg_id`` as on the host - the ids restart in every tile, and equal
+    ids that touch form one component.  Anything else (host masks, a box that leaves its tile or the image) takes the host merge."""
+    if masks and all(torch.is_tensor(m["segmentation"]) and m["segmentation"].is_cuda and m["segmentation"].dim() == 2 for m in masks):
+        table = util._TiledTable(masks)
+        if table.ok and table.inside(shape):
+            dev = table.words.device
+            areas = [m["area"] for m in masks]
+            if any(torch.is_tensor(a) for a in areas):                                  # one download instead of one per comparison
+                areas = torch.stack([torch.as_tensor(a, device=dev).reshape(()) for a in areas]).cpu().tolist()
+            order = sorted(range(len(masks)), key=lambda idx: areas[idx], reverse=True)
+            seg_ids, seg_id = [], 1
+            for idx in order:
+                seg_ids.append(int(masks[idx].get("seg_id", seg_id)))
+                seg_id = seg_ids[-1] + 1
+            if min(seg_ids) >= 1 and max(seg_ids) < 2 ** 31:
+                out = util._merge_tiled_device(table, order, shape, 0, seg_ids=seg_ids)
+                if out is not None:
+                    return out
+    return util.mask_data_to_segmentation(masks, shape=shape, min_object_size=0)

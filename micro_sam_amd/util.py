@@ -1030,14 +1030,152 @@ def _tiled_overlap_scores(masks: List[np.ndarray], boxes: np.ndarray, global_box
     return scores
 
 
+def _tiled_candidate_pairs(global_boxes: np.ndarray) -> np.ndarray:
+    """The pairs ``_tiled_overlap_scores`` scores, from the (int64) global xywh boxes alone: int32 [Np, 2] in the order of its sweep
+    along x, only pairs whose window is not empty (a listed pair of two empty masks would turn 0/0 into a suppression)."""
+    gx0, gy0 = global_boxes[:, 0], global_boxes[:, 1]
+    gx1, gy1 = gx0 + global_boxes[:, 2], gy0 + global_boxes[:, 3]
+    order = np.argsort(gx0, kind="stable")
+    his = np.searchsorted(gx0[order], gx1[order], side="left")
+    pairs = []
+    for rank, i in enumerate(order):
+        js = order[rank + 1:his[rank]]
+        if js.size:
+            hit = (np.minimum(gx1[i], gx1[js]) > np.maximum(gx0[i], gx0[js])) & (np.minimum(gy1[i], gy1[js]) > np.maximum(gy0[i], gy0[js]))
+            js = js[hit]
+            pairs.append(np.stack([np.full(js.shape, i), js], axis=1))
+    return np.concatenate(pairs).astype(np.int32) if pairs else np.zeros((0, 2), np.int32)
+
+
+class _TiledTable:
+    """The record table of csrc/tilemerge.hip for tile-local records whose masks are dense device tensors: ``words`` (the bit masks
+    of all records, packed on the device per run of equal tile shape), per record its first word, tile geometry and boxes, and
+    ``areas`` (int64 [K] on the host: the popcount of every whole tile mask, counted on the device and downloaded once).  ``ok`` is
+    False where a bbox leaves its tile, which the kernels' wrappers refuse."""
+
+    def __init__(self, records):
+        from ._propagate import MAX_OBJECTS, pack_bits
+        masks = [r["segmentation"] for r in records]
+        k = len(masks)
+        self.boxes = np.array([r["bbox"] for r in records]).astype(np.int64).reshape(k, -1)[:, :4]          # .to(torch.long): truncation
+        self.global_boxes = np.array([r["global_bbox"] for r in records]).astype(np.int64).reshape(k, -1)[:, :4]
+        shapes = np.array([tuple(m.shape) for m in masks], dtype=np.int64).reshape(k, 2)
+        wpc, tw = (shapes[:, 0] + 31) // 32, shapes[:, 1]
+        self.word_offset = np.concatenate([[0], np.cumsum(wpc * tw)[:-1]]).astype(np.int64)
+        words, areas = [], []
+        s = 0
+        while s < k:                                     # runs of equal tile shape, at most 64 MiB of dense masks per stack
+            e, limit = s + 1, min(MAX_OBJECTS, max(1, (1 << 26) // max(1, int(shapes[s, 0] * shapes[s, 1]))))
+            while e < k and e - s < limit and tuple(shapes[e]) == tuple(shapes[s]):
+                e += 1
+            stack = torch.stack([m if m.dtype == torch.bool else m != 0 for m in masks[s:e]])
+            words.append(pack_bits(stack).reshape(-1))
+            areas.append(stack.flatten(1).sum(dim=1, dtype=torch.int32))
+            s = e
+        self.words = torch.cat(words)
+        self.areas = fetch_to_host(torch.cat(areas), tag="tile_areas").astype(np.int64)
+        self.geom = np.concatenate([np.stack([wpc, tw], axis=1), self.boxes, self.global_boxes[:, :2]], axis=1)
+        bx, by, bw, bh = (self.boxes[:, c] for c in range(4))
+        self.ok = bool(np.all((bx >= 0) & (by >= 0) & (bw >= 0) & (bh >= 0) & (bx + bw <= tw) & (by + bh <= shapes[:, 0])
+                              & (np.abs(self.global_boxes) < 2 ** 30).all(axis=1)))
+
+    def inside(self, shape) -> bool:
+        g = self.global_boxes
+        return bool(np.all((g[:, 0] >= 0) & (g[:, 1] >= 0) & (g[:, 0] + self.boxes[:, 2] <= shape[1]) & (g[:, 1] + self.boxes[:, 3] <= shape[0])))
+
+    def select(self, idx):
+        idx = np.asarray(idx, dtype=np.int64)
+        return self.word_offset[idx], np.ascontiguousarray(self.geom[idx].astype(np.int32))
+
+
+def _merge_tiled_device(table: _TiledTable, paint_order, shape, min_object_size: int, seg_ids=None) -> Optional[np.ndarray]:
+    """``mask_data_to_segmentation(records, shape, min_object_size)`` for the records ``paint_order`` of ``table`` (already in the
+    stable area-descending paint order, records below ``min_object_size`` left out): msam_paint_tiled, then the device tail (component
+    labelling, size filter, consecutive relabel) and ONE download.  ``seg_ids``: the value each of them paints (records of different
+    tiles may share a ``seg_id``, and equal values that touch are one component); None: distinct values.  Returns None if the
+    labelling reported an open edge (the caller repeats the merge on the host)."""
+    from . import ops
+    h, w = int(shape[0]), int(shape[1])
+    m = len(paint_order)
+    if m == 0:
+        return np.zeros((h, w), dtype="uint32")
+    off, geom = table.select(paint_order)
+    painted = ops.paint_tiled(table.words, off, geom, np.arange(m, dtype=np.int32), h, w)
+    if seg_ids is not None:                                                 # painted value M - r -> the record's seg_id
+        lut = torch.tensor([0] + [int(v) for v in reversed(seg_ids)], dtype=torch.int32, device=painted.device)
+        painted = lut[painted.to(torch.int64)]
+    labels, flag = _painted_to_labels_device(painted, min_object_size)
+    out = fetch_to_host(torch.cat([labels.reshape(-1), flag]), tag="labels")    # one download: the label image + the convergence flag
+    if out[-1] != 0:
+        return None
+    return out[:-1].reshape(h, w).view(np.uint32)
+
+
+def _apply_nms_tiled_device(predictions, min_size, shape, perform_box_nms, nms_thresh, max_size, intersection_over_min) -> Optional[np.ndarray]:
+    """``_apply_nms_tiled`` for records whose masks are dense device tensors, without bringing a mask to the host: the masks are
+    packed to bits where they are, the candidate pairs come from the boxes, ONE msam_tiled_mask_overlaps launch counts their window
+    intersections, the scores and the greedy sweep (O(K + pairs) scalar work) stay on the host in the host path's float32
+    arithmetic, and the survivors are merged by ``_merge_tiled_device``.  Returns None where the host path has to answer: a box
+    that leaves its tile or ``shape`` (the host path raises or clips as before), or a labelling that did not converge."""
+    from . import ops
+    table = _TiledTable(predictions)
+    if not (table.ok and table.inside(shape)):
+        return None
+    areas = table.areas
+    sel = np.arange(len(predictions))
+    if min_size > 0:
+        sel = sel[areas[sel] > min_size]
+    if max_size is not None:
+        sel = sel[areas[sel] < max_size]
+    if sel.size == 0:
+        return np.zeros(shape, dtype="uint32")
+    scores = np.array([np.float32(predictions[i]["predicted_iou"]) * np.float32(predictions[i]["stability_score"]) for i in sel],
+                      dtype=np.float32)
+    if perform_box_nms:
+        dev = table.words.device
+        xyxy = torch.tensor([predictions[i]["global_bbox"] for i in sel], dtype=torch.float32, device=dev)
+        xyxy[:, 2] += xyxy[:, 0]
+        xyxy[:, 3] += xyxy[:, 1]
+        keep = ops.box_nms(xyxy, torch.as_tensor(scores, device=dev), nms_thresh).cpu().tolist()
+    else:
+        pairs = _tiled_candidate_pairs(table.global_boxes[sel])
+        off, geom = table.select(sel)
+        inter = fetch_to_host(ops.tiled_mask_overlaps(table.words, off, geom, pairs), tag="tile_inter").astype(np.float32)
+        a = areas[sel].astype(np.float32)
+        ai, aj = a[pairs[:, 0]], a[pairs[:, 1]]
+        den = np.minimum(ai, aj) if intersection_over_min else ai + aj - inter
+        with np.errstate(divide="ignore", invalid="ignore"):
+            v = inter / den
+        hit = pairs[~(v <= np.float32(nms_thresh))]                                     # nan (0/0) suppresses, as `<=` does
+        partners = {}
+        for i, j in hit.tolist():
+            partners.setdefault(i, []).append(j)
+            partners.setdefault(j, []).append(i)
+        suppressed = np.zeros(sel.size, dtype=bool)
+        keep = []
+        for i in np.argsort(-scores.astype(np.float64), kind="stable").tolist():
+            if suppressed[i]:
+                continue
+            keep.append(i)
+            suppressed[partners.get(i, [])] = True
+    kept = [int(sel[i]) for i in keep]
+    paint_order = [i for i in sorted(kept, key=lambda i: areas[i], reverse=True) if areas[i] >= min_size]
+    return _merge_tiled_device(table, paint_order, shape, min_size)
+
+
 def _apply_nms_tiled(predictions, min_size, shape, perform_box_nms, nms_thresh, max_size, intersection_over_min) -> np.ndarray:
-    """``apply_nms`` for tile-local records (reference util.py:1876-1957 with ``is_tiled``): a host computation in the
-    reference as well (``_batched_tiled_mask_nms`` moves everything to the CPU).  The masks come off the device once."""
+    """``apply_nms`` for tile-local records (reference util.py:1876-1957 with ``is_tiled``).  Records whose masks are dense
+    device tensors stay there (``_apply_nms_tiled_device``: msam_tiled_mask_overlaps + msam_paint_tiled); numpy / CPU records take
+    the reference's host computation (``_batched_tiled_mask_nms`` moves everything to the CPU) below."""
     from . import ops
     if perform_box_nms and intersection_over_min:
         raise ValueError("intersection_over_min needs mask NMS (perform_box_nms=False)")
     if shape is None:
         shape = _infer_tiled_shape(predictions)
+    if all(torch.is_tensor(p["segmentation"]) and p["segmentation"].is_cuda and p["segmentation"].dim() == 2 for p in predictions):
+        out = _apply_nms_tiled_device(predictions, min_size, shape, perform_box_nms, nms_thresh, max_size, intersection_over_min)
+        if out is not None:
+            return out
 
     def dense(p):
         m = p["segmentation"]
@@ -1087,7 +1225,9 @@ def apply_nms(predictions: List[Dict[str, Any]], min_size: int, shape: Optional[
     score = predicted_iou * stability_score - box NMS (``msam_box_nms``) or mask NMS on IoU / intersection-over-min
     (``msam_mask_nms``: popcount of AND over bit masks instead of the reference's ``masks_flat @ masks_flat.T``) - and merge
     of the survivors to a label image.  Tile-local predictions (records with a ``global_bbox``, as
-    ``inference.batched_tiled_inference`` returns them) take the reference's host path (``_apply_nms_tiled``)."""
+    ``inference.batched_tiled_inference`` returns them) go to ``_apply_nms_tiled``: with dense device masks the cross-tile
+    window overlaps and the merge run on the device (``msam_tiled_mask_overlaps``, ``msam_paint_tiled``) and no mask is copied
+    to the host; numpy / CPU records take the reference's host computation."""
     from . import ops
     from ._vendored import pack_bits
     if len(predictions) == 0:
@@ -1215,6 +1355,17 @@ def masks_to_segmentation_device(bits: torch.Tensor, areas: torch.Tensor, keep: 
     order = torch.sort(key, descending=True, stable=True).indices.to(torch.int32).contiguous()
     k_dev = sel.sum().to(torch.int32).reshape(1)
     painted = ops.paint_label_image_dev(bits, order, k_dev, h, w)
+    return _painted_to_labels_device(painted, min_object_size, with_background)
+
+
+def _painted_to_labels_device(painted: torch.Tensor, min_object_size: int = 0, with_background: bool = False):
+    """The tail of ``mask_data_to_segmentation`` from a painted int32 [H,W] image on the device: 4-connected components of equal
+    value in the reference's numbering, drop the components smaller than ``min_object_size`` and (``with_background``) the largest
+    one counting label 0, relabel consecutively.  Returns (labels int32 [H,W], converged flag int32[1] - must read 0); no host
+    synchronisation."""
+    from . import ops
+    h, w = int(painted.shape[0]), int(painted.shape[1])
+    dev = painted.device
     roots32, flag = ops.label_components_async(painted, passes=2)
     roots = roots32.to(torch.int64)
     fg = roots >= 0
