@@ -71,7 +71,8 @@ typedef struct {
                                             group followed by exact GELU; applied after bias/table/resid */
     const float* ln_w; const float* ln_b; float ln_eps;    /* [256] (mode 1) or [64] (mode 2) */
     /* fp8 operands (BASELINE config 5): a_dtype = MSAM_FP8 -> A and W are OCP e4m3 bytes (lda / ldw / K in elements,
-     * K % 128 == 0, N % 256 == 0), out = act(acc * row_scale[m] * col_scale[n] + bias + resid); 0 / MSAM_BF16 = bf16;
+     * K % 128 == 0, N % 256 == 0), out = act(acc * row_scale[m] * col_scale[n] + bias + resid) in fp32 or bf16 (an fp16
+     * output is refused); 0 / MSAM_BF16 = bf16;
      * MSAM_F16 = A and W are IEEE fp16 (128 x 128 tile kernel, plain / grouped launches; 16-bit outputs follow out_dtype:
      * MSAM_F16 -> fp16, MSAM_BF16 -> bf16) */
     int32_t a_dtype;

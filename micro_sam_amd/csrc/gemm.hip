@@ -1309,10 +1309,10 @@ extern "C" int msam_gemm_bf16(const msam_gemm_t* p, void* stream) {
     if (p->a_dtype == MSAM_FP8) {
         // fp8 e4m3 operands: 256 x 256 tile kernel only (the encoder's projections)
         if (p->N % G2 || p->K % 128 || (p->lda % 16) || (p->ldw % 16) || p->ln_mode || p->out_mode == 2 || p->table ||
-            p->use_glds || !p->row_scale || !p->col_scale ||
+            p->use_glds || !p->row_scale || !p->col_scale || p->out_dtype == MSAM_F16 ||
             (p->resid && (p->resid_dtype != MSAM_F32 || p->resid_rows))) {
             msam_set_error("msam_gemm_bf16(fp8): need N % 256 == 0, K % 128 == 0, lda / ldw % 16 == 0, row_scale and col_scale, plain or qkv-split "
-                           "output, fp32 residual without row wrap, no table");
+                           "output in fp32 or bf16 (the kernel packs bf16), fp32 residual without row wrap, no table");
             return 1;
         }
         static bool attr8 = false;
@@ -1335,6 +1335,9 @@ extern "C" int msam_gemm_bf16(const msam_gemm_t* p, void* stream) {
         return msam_check_launch("msam_gemm_bf16(fp8)");
     }
     int tiles = ((p->M + BM - 1) / BM) * (p->N / BN);
+    // gemm256_kernel / gemm2w_kernel pack a 16-bit output by their OPERAND type: a 16-bit output of the other type (fp16 operands with a bf16
+    // output, bf16 operands with an fp16 output) stays on the 128 x 128 kernel, whose pack follows out_dtype
+    const bool out_ok256 = f16 ? p->out_dtype != MSAM_BF16 : p->out_dtype != MSAM_F16;
     // large shapes (the encoder's projections): 256 x 256 tile kernel.  MSAM_GEMM256=0 keeps the 128 x 128 kernel (A/B runs)
     static int use256 = -1, staging256 = 0;
     if (use256 < 0) {
@@ -1345,7 +1348,7 @@ extern "C" int msam_gemm_bf16(const msam_gemm_t* p, void* stream) {
     if (!MSAM_EXPERIMENTS && (staging256 < 0 || staging256 > 3)) staging256 = G2_DEFAULT_STAGING;
     // staging 4: the two-workgroups-per-CU kernel (256 x 128 tiles, LDS-DMA ring, epilogue from the accumulators)
     // (its operand offsets are 32-bit: operands of 2 GiB and more stay on the 256 x 256 kernel)
-    if (MSAM_EXPERIMENTS && use256 && staging256 == 4 && (double)p->M * p->lda * 2 < 2147483648.0 && (double)p->N * p->ldw * 2 < 2147483648.0 && p->split_k <= 1 && (!f16 || p->out_dtype != MSAM_BF16) && !p->use_glds &&
+    if (MSAM_EXPERIMENTS && use256 && staging256 == 4 && (double)p->M * p->lda * 2 < 2147483648.0 && (double)p->N * p->ldw * 2 < 2147483648.0 && p->split_k <= 1 && out_ok256 && !p->use_glds &&
         ((p->M + G2 - 1) / G2) * (p->N / G2) >= 256 && p->N % GW_BN == 0 && p->K % GW_BK == 0 && p->lda % 8 == 0 && p->ldw % 8 == 0 &&
         p->out_mode != 2 && p->out_mode != 3 && !p->table && (!p->resid || (p->resid_dtype == MSAM_F32 && !p->resid_rows))) {
         static bool attr2w = false;
@@ -1383,7 +1386,7 @@ extern "C" int msam_gemm_bf16(const msam_gemm_t* p, void* stream) {
     }
     // (measured: 3 - 14 % faster than the 128 x 128 kernel from one workgroup per CU upwards, slower below)
     // (fp16 operands: 16-bit outputs of this kernel are then fp16 as well - the encoder's fp16 mode; a bf16 output is not offered)
-    if (use256 && p->split_k <= 1 && (!f16 || p->out_dtype != MSAM_BF16) && !p->use_glds && ((p->M + G2 - 1) / G2) * (p->N / G2) >= 256 && p->N % G2 == 0 &&
+    if (use256 && p->split_k <= 1 && out_ok256 && !p->use_glds && ((p->M + G2 - 1) / G2) * (p->N / G2) >= 256 && p->N % G2 == 0 &&
         p->out_mode != 2 && p->out_mode != 3 && !p->table && (!p->resid || (p->resid_dtype == MSAM_F32 && !p->resid_rows))) {
         static bool attr256 = false;
         if (!attr256) {
