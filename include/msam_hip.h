@@ -988,6 +988,23 @@ int msam_paint_max(const uint32_t* bits, const int32_t* ids, const uint8_t* keep
                    void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Tracking P objects through a time series (tracking.track_objects_in_timeseries; reference micro_sam/sam_annotator/util.py:561-579
+ * _compute_movement / _shift_object; csrc/track.hip): the centre of a bit mask and its shift by a per-object motion, on the bit masks
+ * and within the limits of the section above.  Bits of rows >= H in the last word row of an input are ignored; the same bits of an
+ * output are zero.  No workspace, no allocation, no synchronisation; integer sums only.  A refusal returns non-zero with a message
+ * that names the entry point and leaves the outputs untouched.
+ * ------------------------------------------------------------------------------------------------- */
+/* out: int64 [P, 3] = (count, sum of y, sum of x) over the set pixels, exact (64-bit accumulators throughout).  The centre of mass is
+ * the caller's division: (double)sum / (double)count is bit for bit np.mean of the index arrays.  Two launches. */
+int msam_mask_moments(const uint32_t* bits, int32_t P, int32_t H, int32_t W, int64_t* out, void* stream);
+/* bits_out[p](y, x) = bits_in[p](src_y(y), src_x(x)), zero where either source is invalid; shifts: fp64 [P, 2] = (sy, sx) per object on
+ * the device.  Per axis of length n and shift s, in fp64 with every step rounded on its own: cc = (double)i - s, valid = cc >= 0 &&
+ * cc <= n - 1, src = (int)floor(cc + 0.5) - scipy.ndimage.shift(mask, (sy, sx), order=0, prefilter=False) with mode "constant" and
+ * cval 0, evaluated per index (src(i) - i changes along the axis where s lies within rounding of k + 1/2).  A NaN or infinite shift
+ * gives an empty mask.  bits_out must not be bits_in.  One launch. */
+int msam_mask_shift(const uint32_t* bits_in, int32_t P, int32_t H, int32_t W, const double* shifts, uint32_t* bits_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Cross-tile mask NMS and label merge of tile-local records (util.apply_nms on records with a global_bbox; reference
  * micro_sam/util.py:1698-1747 _calculate_tiled_mask_overlap_matrix, :1773-1848 mask_data_to_segmentation; csrc/tilemerge.hip).
  * Both entry points read a RECORD TABLE in device memory:

@@ -291,6 +291,8 @@ _PROTOS = {
     "msam_adapter_bf16": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "msam_tiled_mask_overlaps": (_i32, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp]),
     "msam_paint_tiled": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "msam_mask_moments": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "msam_mask_shift": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
 }
 OPTIONAL = set()
 

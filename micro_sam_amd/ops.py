@@ -1244,3 +1244,4 @@ from ._depthconv import depth_conv3  # noqa: E402,F401  (csrc/conv3d.hip's depth
 from ._conv3d import column_sums, conv3d_k3, conv3d_k3_wgrad, instance_norm_apply, instance_norm_backward, instance_norm_stats  # noqa: E402,F401  (csrc/conv3d.hip; same arrangement)
 from ._adapter import adapter_  # noqa: E402,F401  (csrc/adapter.hip; same arrangement)
 from ._tilemerge import paint_tiled, tiled_mask_overlaps  # noqa: E402,F401  (csrc/tilemerge.hip; same arrangement)
+from ._track import mask_moments, mask_shift  # noqa: E402,F401  (csrc/track.hip; same arrangement)
