@@ -275,10 +275,13 @@ int msam_fold_attn_set_dma(int32_t on);
  * hand-over stream kernel, 3 = default or 2), "up_gelu16" (1 = the up-scaling's GELUs in packed fp16 arithmetic, default in the fp16 decoder build;
  * 0 = packed fp32), "amg_range_map" (1 = default: the AMG path asks the decoder for the range map of its low-res logits and hands
  * it to the post-processing; 0 = it does not: the launches of msam_upscale_fused_out and msam_postprocess_masks16.  The entry points
- * below do what they are asked whatever its value: the caller that owns both ends reads it once per call, msam_tune_get).
+ * below do what they are asked whatever its value: the caller that owns both ends reads it once per call, msam_tune_get),
+ * "prompt_prefix" (1 = default: the mask generator keeps msam_decoder_prompt_prefix blocks per point grid and decodes with
+ * msam_decoder_forward_masks_prefixed; 0 = msam_decoder_forward_masks for every tile; read by that caller like "amg_range_map"),
+ * "t2i_shared_group" (prompts per workgroup of the decoder's layer-0 token->image attention: 4 = default, 8, 16; same bits).
  * Returns 0, 1 for an unknown key. */
 int msam_tune_set(const char* key, int32_t value);
-/* the present value of "amg_range_map" (the one knob a caller decides on); 1 for any other key */
+/* the present value of "amg_range_map" or "prompt_prefix" (the knobs a caller decides on); 1 for any other key */
 int msam_tune_get(const char* key, int32_t* value);
 /* debug hook: phase timing of the folded image->token kernel (see csrc/decfold.hip, tools/i2t_timing.py) */
 int msam_debug_i2t_timing(int32_t enable, uint64_t* host_out);
@@ -581,6 +584,25 @@ int msam_decoder_forward_masks(const msam_decoder_t* dec, const msam_mask_prompt
                                const void* image_state, const float* points, const int32_t* labels, int32_t Np,
                                const float* boxes, const float* mask_input, int32_t P, int32_t multimask, float* low_res,
                                float* iou, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The prompt-only head of a decode, computed once for prompts that stay the same from image to image (the point grid of the automatic
+ * mask generator: one grid per crop size, the same for every tile, slice and frame).  Nothing in front of layer 0's token->image
+ * attention reads the image: msam_decoder_prompt_prefix runs those launches (prompt tokens, layer 0's self attention, its out
+ * projection, norm1 and the q product of the token->image attention) through the kernels a decode uses and leaves, in the caller's
+ * block of msam_decoder_prompt_prefix_bytes(P, Nt) bytes (Nt = 5 + Np + (boxes ? 2 : (Np > 0 ? 1 : 0)); device memory, 256-byte
+ * aligned): the tokens' positional encoding fp32 [P Nt, 256], the queries behind norm1 fp32 [P Nt, 256], that q 16-bit [P Nt, 128].
+ * msam_decoder_forward_masks_prefixed is msam_decoder_forward_masks without those launches: it reads the block in place, never
+ * writes it, and gives the same bits.  The block belongs to (dec's weights, points, labels, boxes, P, the "tok_fuse" route); one
+ * block serves any number of images and concurrent streams.  `workspace` as for a decode of P prompts.  With
+ * MSAM_DEBUG_DEC_LAYERS set the block is ignored. */
+int64_t msam_decoder_prompt_prefix_bytes(int32_t P, int32_t Nt);
+int msam_decoder_prompt_prefix(const msam_decoder_t* dec, const float* points, const int32_t* labels, int32_t Np,
+                               const float* boxes, int32_t P, void* prefix, void* workspace, int64_t workspace_bytes, void* stream);
+int msam_decoder_forward_masks_prefixed(const msam_decoder_t* dec, const msam_mask_prompt_t* mask_w, const void* consts,
+                                        const void* image_state, const float* points, const int32_t* labels, int32_t Np,
+                                        const float* boxes, const float* mask_input, const void* prefix, int32_t P,
+                                        int32_t multimask, float* low_res, float* iou, void* workspace, int64_t workspace_bytes,
+                                        void* stream);
 
 /* The prompt encoder and the mask decoder as stand-alone module calls (the reference calls them directly:
  * micro_sam/training/trainable_sam.py:96-106 `sam.prompt_encoder(points, boxes, masks)` and

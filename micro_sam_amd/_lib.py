@@ -140,6 +140,10 @@ _PROTOS = {
     "msam_uncrop_bits": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "msam_decoder_forward_masks": (_i32, [C.POINTER(DecoderParams), C.POINTER(MaskPromptParams), _vp, _vp, _vp, _vp, _i32, _vp, _vp,
                                           _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "msam_decoder_prompt_prefix_bytes": (_i64, [_i32, _i32]),
+    "msam_decoder_prompt_prefix": (_i32, [C.POINTER(DecoderParams), _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
+    "msam_decoder_forward_masks_prefixed": (_i32, [C.POINTER(DecoderParams), C.POINTER(MaskPromptParams), _vp, _vp, _vp, _vp, _i32, _vp,
+                                                   _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     "msam_i2t_fold_workspace_bytes": (_i64, [_i32]),
     "msam_i2t_fold_layer": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i64, _vp]),
     "msam_profile_enable": (_i32, [_i32]),
@@ -333,7 +337,7 @@ def load() -> C.CDLL:
 
 
 def tune_get(key: str) -> int:
-    """Present value of a knob the callers of the library decide on (``msam_tune_get``: "amg_range_map")."""
+    """Present value of a knob the callers of the library decide on (``msam_tune_get``: "amg_range_map", "prompt_prefix")."""
     v = _i32(0)
     check(load().msam_tune_get(key.encode(), C.byref(v)), "msam_tune_get")
     return int(v.value)

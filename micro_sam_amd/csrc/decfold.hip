@@ -788,6 +788,10 @@ extern "C" int msam_fold_attn_set_dma(int32_t on) { g_fold_attn_dma = on; return
 //   "amg_range_map"   1 (default) = the AMG path asks the decoder for the range map of its low-res logits and hands it to the post-processing;
 //                     0 = it does not: the launches of msam_upscale_fused_out and msam_postprocess_masks16.  The library's entry points do not
 //                     read this knob - the caller that owns both ends does, once per call (msam_tune_get; predictor.py)
+//   "prompt_prefix"   1 (default) = the mask generator keeps the prompt-only head of the decode (msam_decoder_prompt_prefix) per point grid
+//                     and decodes with msam_decoder_forward_masks_prefixed; 0 = msam_decoder_forward_masks for every tile.  Read by that
+//                     caller, once per call (msam_tune_get; instance_segmentation.py)
+//   "t2i_shared_group" prompts per workgroup of the layer-0 token->image attention on the shared K / V^T: 4 (default), 8 or 16; same bits
 extern int g_tune_i2t_wg_per_cu, g_tune_chain_variant, g_tune_chain_tmask, g_tune_up_gelu16, g_tune_up_ln_two_pass, g_tune_up_centred;
 void msam_gemm_set_dbg(int v);
 void msam_gemm_set_gw(int delay, int cls);
@@ -797,6 +801,7 @@ extern int g_tune_tok_fuse;
 extern int g_tune_chain_handover, g_tune_chain_handover_ring;
 extern int g_tune_mlp_split_fused;
 extern int g_tune_amg_range_map;
+extern int g_tune_t2i_shared_group, g_tune_prompt_prefix;
 extern int g_tune_sgemm_bufs, g_tune_srel_mfma, g_tune_sgemm_small_below, g_tune_si2t_dbg, g_tune_si2t_late_us, g_tune_sattn_allh;
 int g_tune_dec_chain = 1, g_tune_dec_chain_min_p = 128;
 extern "C" int msam_tune_set(const char* key, int32_t value) {
@@ -812,6 +817,8 @@ extern "C" int msam_tune_set(const char* key, int32_t value) {
     else if (k == "up_ln_two_pass") g_tune_up_ln_two_pass = value;
     else if (k == "up_centred") g_tune_up_centred = value;
     else if (k == "amg_range_map") g_tune_amg_range_map = value;
+    else if (k == "t2i_shared_group") g_tune_t2i_shared_group = value;
+    else if (k == "prompt_prefix") g_tune_prompt_prefix = value;
     else if (k == "gemm_dbg") msam_gemm_set_dbg(value);
     else if (k == "gw_delay") msam_gemm_set_gw(value, -1);
     else if (k == "gw_class") msam_gemm_set_gw(-2, value);
@@ -829,10 +836,10 @@ extern "C" int msam_tune_set(const char* key, int32_t value) {
     else { msam_set_error("msam_tune_set: unknown key"); return 1; }
     return 0;
 }
-// the present value of a knob the callers of the library decide on ("amg_range_map"); 1 for any other key
+// the present value of a knob the callers of the library decide on ("amg_range_map", "prompt_prefix"); 1 for any other key
 extern "C" int msam_tune_get(const char* key, int32_t* value) {
     const std::string k = key ? key : "";
-    if (!value || k != "amg_range_map") { msam_set_error("msam_tune_get: unknown key"); return 1; }
-    *value = g_tune_amg_range_map;
+    if (!value || (k != "amg_range_map" && k != "prompt_prefix")) { msam_set_error("msam_tune_get: unknown key"); return 1; }
+    *value = k == "prompt_prefix" ? g_tune_prompt_prefix : g_tune_amg_range_map;
     return 0;
 }

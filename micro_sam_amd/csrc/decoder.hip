@@ -397,36 +397,59 @@ __global__ __launch_bounds__(256) void t2i_attn_kernel(const u16* __restrict__ q
 }
 
 // Token -> image attention on the SHARED layer-0 K / V^T (prompt independent, L2 resident) for up to 8 tokens per prompt:
-// one workgroup per (4 prompts, head), i.e. two 16-column score tiles (column = (prompt & 1) * 8 + token) per K / V^T
-// fragment - a quarter of the L2 traffic of the one-prompt-per-workgroup kernel above, which is L2-bandwidth bound.
-__global__ __launch_bounds__(256) void t2i_shared4_kernel(const u16* __restrict__ qtok, const u16* __restrict__ kimg,
-                                                          const u16* __restrict__ vT, int P, int Nt, u16* __restrict__ out) {
-    __shared__ float red[4][32][20];      // per wave: [column][m, l, o[16]] (+pad)
+// one workgroup per (G prompts, head), i.e. G / 2 16-column score tiles (column = (prompt & 1) * 8 + token) per K / V^T
+// fragment - 1 / G of the L2 traffic of the one-prompt-per-workgroup kernel above, which is L2-bandwidth bound, and G / 2
+// independent score tiles per step of a wave's serial chain.  A score column is one (prompt, token) and the MFMA treats columns
+// independently: the key quarter per wave, the 32-key step, the per-step arithmetic and the four-way merge are the same for
+// every G, so every G gives the same bits (msam_tune_set "t2i_shared_group": 4 = default, 8, 16).  Measured per launch of 1024 prompts
+// (profiles/r14_prompt_prefix.md): 101.9 us (4), 92.5 (8), 94.3 (16); the benchmark with its three decode lanes does not tell them apart,
+// so the default stays at the grouping of rounds 1 - 13.
+// (Two workgroups per CU as the launch bound keep a wave within 256 registers: the compiler then takes the MFMA results in VGPRs, where
+//  the softmax reads them, instead of AGPRs with a v_accvgpr_read / _write per value - 17 % of the key loop's instructions.)
+template <int G>
+__global__ __launch_bounds__(256, 2) void t2i_shared_kernel(const u16* __restrict__ qtok, const u16* __restrict__ kimg,
+                                                         const u16* __restrict__ vT, int P, int Nt, u16* __restrict__ out) {
+    constexpr int NT = G / 2;                   // score tiles per workgroup
+    __shared__ float red[4][NT * 16][20];       // per wave: [column][m, l, o[16]] (+pad)
     const int pg = blockIdx.x >> 3, head = blockIdx.x & 7;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
     const u16* kb = kimg + (long)head * T * 16;
     const u16* vb = vT + ((long)head * 16 + fr) * T;
     const int tk = fr & 7;
-    uint4 qf[2];
+    // tail group (P % G != 0): columns without a prompt work on a zero q and are not written; score tiles without one are not merged.
+    // (No branch on them in the key loop: it would cut the loop body into one block per tile and keep the tiles' chains apart.)
+    const int left = P - pg * G;
+    const int nt = left >= G ? NT : (left + 1) >> 1;
+    uint4 qf[NT];
 #pragma unroll
-    for (int n = 0; n < 2; ++n) {
-        const int p = pg * 4 + n * 2 + (fr >> 3);
+    for (int n = 0; n < NT; ++n) {
+        const int p = pg * G + n * 2 + (fr >> 3);
         qf[n] = make_uint4(0, 0, 0, 0);
         if (fg < 2 && tk < Nt && p < P) qf[n] = *(const uint4*)(qtok + ((long)p * Nt + tk) * CI + head * 16 + fg * 8);
     }
-    f32x4_t o[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    float m[2] = {NEG_BIG, NEG_BIG}, l[2] = {0.f, 0.f};
-    const int t_begin = wave * (T / 4), t_end = t_begin + T / 4;
-    for (int t0 = t_begin; t0 < t_end; t0 += 32) {
-        uint4 ka0 = make_uint4(0, 0, 0, 0), ka1 = ka0;
-        if (fg < 2) {
-            ka0 = *(const uint4*)(kb + (long)(t0 + fr) * 16 + fg * 8);
-            ka1 = *(const uint4*)(kb + (long)(t0 + 16 + fr) * 16 + fg * 8);
-        }
-        const uint2 v0 = *(const uint2*)(vb + t0 + fg * 4), v1 = *(const uint2*)(vb + t0 + 16 + fg * 4);
-        const uint4 va = make_uint4(v0.x, v0.y, v1.x, v1.y);
+    f32x4_t o[NT];
+    float m[NT], l[NT];
 #pragma unroll
-        for (int n = 0; n < 2; ++n) {
+    for (int n = 0; n < NT; ++n) { o[n] = f32x4_t{0.f, 0.f, 0.f, 0.f}; m[n] = NEG_BIG; l[n] = 0.f; }
+    const int t_begin = wave * (T / 4), t_end = t_begin + T / 4;
+    // the K / V^T fragments of a step are requested one step ahead (the last step asks for its own again: in bounds, unused)
+    uint4 ka0 = make_uint4(0, 0, 0, 0), ka1 = ka0, kn0 = ka0, kn1 = ka0;
+    if (fg < 2) {
+        kn0 = *(const uint4*)(kb + (long)(t_begin + fr) * 16 + fg * 8);
+        kn1 = *(const uint4*)(kb + (long)(t_begin + 16 + fr) * 16 + fg * 8);
+    }
+    uint2 vn0 = *(const uint2*)(vb + t_begin + fg * 4), vn1 = *(const uint2*)(vb + t_begin + 16 + fg * 4);
+    for (int t0 = t_begin; t0 < t_end; t0 += 32) {
+        ka0 = kn0; ka1 = kn1;
+        const uint4 va = make_uint4(vn0.x, vn0.y, vn1.x, vn1.y);
+        const int tn = t0 + 32 < t_end ? t0 + 32 : t0;
+        if (fg < 2) {
+            kn0 = *(const uint4*)(kb + (long)(tn + fr) * 16 + fg * 8);
+            kn1 = *(const uint4*)(kb + (long)(tn + 16 + fr) * 16 + fg * 8);
+        }
+        vn0 = *(const uint2*)(vb + tn + fg * 4); vn1 = *(const uint2*)(vb + tn + 16 + fg * 4);
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
             f32x4_t s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
             s0 = mfma16d(ka0, qf[n], s0);
             s1 = mfma16d(ka1, qf[n], s1);
@@ -447,7 +470,7 @@ __global__ __launch_bounds__(256) void t2i_shared4_kernel(const u16* __restrict_
         }
     }
 #pragma unroll
-    for (int n = 0; n < 2; ++n) {
+    for (int n = 0; n < NT; ++n) {
         float ln = l[n];
         ln += __shfl_xor(ln, 16); ln += __shfl_xor(ln, 32);
         if (fg == 0) { red[wave][n * 16 + fr][0] = m[n]; red[wave][n * 16 + fr][1] = ln; }
@@ -455,8 +478,8 @@ __global__ __launch_bounds__(256) void t2i_shared4_kernel(const u16* __restrict_
         for (int r = 0; r < 4; ++r) red[wave][n * 16 + fr][2 + fg * 4 + r] = o[n][r];
     }
     __syncthreads();
-    if (wave < 2) {                                  // wave n merges score tile n: lane (column fr, fg) -> o[d = fg*4 + r]
-        const int n = wave, c = n * 16 + fr, p = pg * 4 + n * 2 + (fr >> 3);
+    for (int n = wave; n < nt; n += 4) {             // wave w merges score tiles w, w + 4: lane (column fr, fg) -> o[d = fg*4 + r]
+        const int c = n * 16 + fr, p = pg * G + n * 2 + (fr >> 3);
         if (tk < Nt && p < P) {
             const float mm = fmaxf(fmaxf(red[0][c][0], red[1][c][0]), fmaxf(red[2][c][0], red[3][c][0]));
             float ll = 0.f, oo[4] = {0.f, 0.f, 0.f, 0.f};
@@ -633,7 +656,21 @@ extern int g_tune_dec_chain, g_tune_dec_chain_min_p, g_tune_chain_variant, g_tun
 // Default off; kept as a tested option.
 int g_tune_tok_fuse = 0;
 int g_tune_mlp_split_fused = 1;           // msam_tune_set "mlp_split_fused": 0 = fp32 hidden + separate cast launch (the A/B and test form)
+// msam_tune_set "t2i_shared_group": prompts per workgroup of t2i_shared_kernel - 4 (default, the grouping of rounds 1 - 13), 8 or 16; same bits
+int g_tune_t2i_shared_group = 4;
+// msam_tune_set / msam_tune_get "prompt_prefix": read by the CALLER that keeps the blocks (instance_segmentation.py), once per call; 0 = it
+// keeps none and every decode runs the prompt-only launches itself.  The entry points do what they are asked
+int g_tune_prompt_prefix = 1;
 namespace {
+// What the decoder computes from the prompts and the weights alone (msam_decoder_prompt_prefix): the caller's block, read-only for a decode
+struct Prefix { float* qpe; float* queries; u16* q; };       // qpe [M,256], queries behind layer 0's norm1 [M,256], layer-0 t2i q [M,128]
+long prefix_bytes(int P, int Nt) { const long M = (long)P * Nt; return 2 * ((M * C * 4 + 255) & ~255L) + ((M * CI * 2 + 255) & ~255L); }
+Prefix carve_prefix(void* base, int P, int Nt) {
+    const long M = (long)P * Nt, f = (M * C * 4 + 255) & ~255L;
+    Prefix x; char* p = (char*)base;
+    x.qpe = (float*)p; x.queries = (float*)(p + f); x.q = (u16*)(p + 2 * f);
+    return x;
+}
 struct Work {
     float *qpe, *queries, *tmp; u16 *a, *b, *qs, *ks, *vs, *attn_tok, *mlp_h;
     u16 *keys, *kimg, *vT, *qimg, *attn_img, *up1; float* pre;
@@ -676,16 +713,16 @@ Work carve_work(void* base, int P, int Nt) {
 
 // token -> image attention over the per-prompt stream w.keys: folded form (one pass over the stream, decfold.hip) for
 // up to 8 tokens per prompt, explicit K / V^T projection + attention kernel otherwise
-int t2i_stream(const Ctx& cx, const Work& w, const Consts& c, int idx, const msam_attn_w_t& aw, int P, int Nt, bool blocked = false) {
+int t2i_stream(const Ctx& cx, const Work& w, const Consts& c, int idx, const msam_attn_w_t& aw, int P, int Nt, bool blocked, const u16* qs) {
     const long R = (long)P * T;
     if (Nt <= 8) {
         // workspace of the folded form = the (then unused) K / V^T / q / attention stream buffers, contiguous in `Work`
         const int64_t avail = (int64_t)((char*)w.up1 - (char*)w.kimg);
-        return msam_t2i_fold_attention(w.keys, blocked ? 2 : 0, w.qs, P, Nt, aw.k_w, c.tab_k[idx], aw.v_w, aw.v_b, w.attn_tok, w.kimg,
+        return msam_t2i_fold_attention(w.keys, blocked ? 2 : 0, qs, P, Nt, aw.k_w, c.tab_k[idx], aw.v_w, aw.v_b, w.attn_tok, w.kimg,
                                        avail, cx.s);
     }
     if (int e = wsgemm_kv(cx, w.keys, c.wkv[idx], c.bkv[idx], c.pe_k[idx], (int)R, w.kimg, w.vT)) return e;
-    hipLaunchKernelGGL(t2i_attn_kernel, dim3(P * 8), dim3(256), 0, cx.s, w.qs, w.kimg, w.vT, 0, Nt, w.attn_tok);
+    hipLaunchKernelGGL(t2i_attn_kernel, dim3(P * 8), dim3(256), 0, cx.s, qs, w.kimg, w.vT, 0, Nt, w.attn_tok);
     return msam_check_launch("t2i_attn");
 }
 
@@ -710,7 +747,8 @@ int decoder_run(const msam_decoder_t* dec, const msam_mask_prompt_t* mask_w, con
                 const void* image_state, const float* points, const int32_t* labels, int32_t Np,
                 const float* boxes, const float* mask_input, const float* sparse, int32_t Ns, const float* dense,
                 const float* embedding, int32_t P, int32_t multimask,
-                float* low_res, float* iou, void* workspace, int64_t workspace_bytes, void* stream);
+                float* low_res, float* iou, void* workspace, int64_t workspace_bytes, void* stream,
+                const Prefix* pf_in = nullptr, const Prefix* pf_out = nullptr);
 }
 
 extern "C" int msam_decoder_forward_masks(const msam_decoder_t* dec, const msam_mask_prompt_t* mask_w, const void* consts,
@@ -719,6 +757,35 @@ extern "C" int msam_decoder_forward_masks(const msam_decoder_t* dec, const msam_
                                           float* low_res, float* iou, void* workspace, int64_t workspace_bytes, void* stream) {
     return decoder_run(dec, mask_w, consts, image_state, points, labels, Np, boxes, mask_input, nullptr, 0, nullptr, nullptr, P,
                        multimask, low_res, iou, workspace, workspace_bytes, stream);
+}
+
+extern "C" int64_t msam_decoder_prompt_prefix_bytes(int32_t P, int32_t Nt) { return P > 0 && Nt > 0 ? prefix_bytes(P, Nt) : 0; }
+
+namespace {
+int prefix_tokens(const float* points, int32_t Np, const float* boxes) {
+    if (!points) Np = 0;
+    return 5 + Np + (boxes ? 2 : (Np > 0 ? 1 : 0));
+}
+}  // namespace
+
+extern "C" int msam_decoder_prompt_prefix(const msam_decoder_t* dec, const float* points, const int32_t* labels, int32_t Np,
+                                          const float* boxes, int32_t P, void* prefix, void* workspace, int64_t workspace_bytes,
+                                          void* stream) {
+    if (!prefix || P <= 0) { msam_set_error("msam_decoder_prompt_prefix: null argument"); return 1; }
+    const Prefix pf = carve_prefix(prefix, P, prefix_tokens(points, Np, boxes));
+    return decoder_run(dec, nullptr, nullptr, nullptr, points, labels, Np, boxes, nullptr, nullptr, 0, nullptr, nullptr, P, 1, nullptr,
+                       nullptr, workspace, workspace_bytes, stream, nullptr, &pf);
+}
+
+extern "C" int msam_decoder_forward_masks_prefixed(const msam_decoder_t* dec, const msam_mask_prompt_t* mask_w, const void* consts,
+                                                   const void* image_state, const float* points, const int32_t* labels, int32_t Np,
+                                                   const float* boxes, const float* mask_input, const void* prefix, int32_t P,
+                                                   int32_t multimask, float* low_res, float* iou, void* workspace,
+                                                   int64_t workspace_bytes, void* stream) {
+    if (!prefix || P <= 0) { msam_set_error("msam_decoder_forward_masks_prefixed: null argument"); return 1; }
+    const Prefix pf = carve_prefix((void*)prefix, P, prefix_tokens(points, Np, boxes));
+    return decoder_run(dec, mask_w, consts, image_state, points, labels, Np, boxes, mask_input, nullptr, 0, nullptr, nullptr, P,
+                       multimask, low_res, iou, workspace, workspace_bytes, stream, &pf, nullptr);
 }
 
 extern "C" int msam_decoder_forward_embeddings(const msam_decoder_t* dec, const void* consts, const void* image_state,
@@ -758,8 +825,11 @@ int decoder_run(const msam_decoder_t* dec, const msam_mask_prompt_t* mask_w, con
                 const void* image_state, const float* points, const int32_t* labels, int32_t Np,
                 const float* boxes, const float* mask_input, const float* sparse, int32_t Ns, const float* dense,
                 const float* embedding, int32_t P, int32_t multimask,
-                float* low_res, float* iou, void* workspace, int64_t workspace_bytes, void* stream) {
-    if (!dec || !consts || !image_state || !low_res || !iou || !workspace || P <= 0) {
+                float* low_res, float* iou, void* workspace, int64_t workspace_bytes, void* stream,
+                const Prefix* pf_in, const Prefix* pf_out) {
+    // pf_out: run the prompt-only head of the decode and leave its results in that block (msam_decoder_prompt_prefix: no image, no outputs);
+    // pf_in: take them from that block instead of computing them
+    if (!dec || !workspace || P <= 0 || (!pf_out && (!consts || !image_state || !low_res || !iou))) {
         msam_set_error("msam_decoder_forward: null argument");
         return 1;
     }
@@ -776,9 +846,21 @@ int decoder_run(const msam_decoder_t* dec, const msam_mask_prompt_t* mask_w, con
     if (Nt > 16) { msam_set_error("msam_decoder_forward: at most 16 tokens per prompt (<= 10 points)"); return 1; }
     if (workspace_bytes < work_bytes(P, Nt)) { msam_set_error("msam_decoder_forward: workspace too small"); return 1; }
     Ctx cx{(hipStream_t)stream, dec->use_glds};
-    Consts c = carve_consts((void*)consts);
-    ImageState im = carve_image((void*)image_state);
+    Consts c{}; ImageState im{};
+    if (consts) c = carve_consts((void*)consts);
+    if (image_state) im = carve_image((void*)image_state);
     Work w = carve_work(workspace, P, Nt);
+    // test hook: MSAM_DEBUG_DEC_LAYERS=0/1 stops the two-way transformer early so that intermediate workspace buffers
+    // can be compared with the oracle's per-layer taps (outputs are then NOT the model's outputs)
+    const char* dbg = getenv("MSAM_DEBUG_DEC_LAYERS");
+    // the hook's contract is the workspace contents: it takes no block and keeps one grouped launch per step
+    if (dbg) pf_in = nullptr;
+    // the positional encoding of the prompt tokens is read-only from prompt_tokens_kernel onwards: with a block it is the block's
+    if (pf_in) w.qpe = pf_in->qpe;
+    if (pf_out) w.qpe = pf_out->qpe;
+    // layer 0 up to its token->image attention reads no image: norm1's output and the q of that attention (the block's, or the workspace's)
+    float* const q_n1 = pf_out ? pf_out->queries : w.queries;
+    u16* const qs_0 = pf_out ? pf_out->q : w.qs;
     const int M = P * Nt;
     const long R = (long)P * T;
     const long n4 = (long)M * C / 4;
@@ -802,15 +884,12 @@ int decoder_run(const msam_decoder_t* dec, const msam_mask_prompt_t* mask_w, con
         hipLaunchKernelGGL(tokens_from_sparse_kernel, dim3(P), dim3(256), 0, cx.s, dec->out_tokens, sparse, Ns, P, Nt, w.qpe,
                            w.queries, w.a);
         CHECK(msam_check_launch("tokens_from_sparse"));
-    } else {
+    } else if (!pf_in) {
         hipLaunchKernelGGL(prompt_tokens_kernel, dim3(P), dim3(256), 0, cx.s, dec->pe_gauss, dec->point_embed, dec->not_a_point,
                            dec->out_tokens, points, labels, Np, boxes, P, Nt, w.qpe, w.queries, w.a);
         CHECK(msam_check_launch("prompt_tokens"));
     }
 
-    // test hook: MSAM_DEBUG_DEC_LAYERS=0/1 stops the two-way transformer early so that intermediate workspace buffers
-    // can be compared with the oracle's per-layer taps (outputs are then NOT the model's outputs)
-    const char* dbg = getenv("MSAM_DEBUG_DEC_LAYERS");
     const int nlayers = dbg ? atoi(dbg) : 2;
     // Chained form (decfold_tok.hip): with one shared source the layer-0 output stream is not written; the layer-1
     // token->image attention and the layer-1 image->token block recompute their tiles of it from the L2-resident source.
@@ -821,54 +900,69 @@ int decoder_run(const msam_decoder_t* dec, const msam_mask_prompt_t* mask_w, con
     void* const oper0 = w.qimg; void* const oper1 = w.attn_img;
     // blocked copies of the shared tables (source, layer-0 q, tabK / tabQ of layer 1) at the end of the attention workspace in vT
     void* const tables = (char*)w.vT + (int64_t)R * CI * 2 - msam_chain_tables_bytes();
-    if (chain) CHECK(msam_chain_prepare_tables(im.src_bf16, im.q0, c.tab_k[1], c.tab_q[1], tables, cx.s));
+    if (chain && !pf_out) CHECK(msam_chain_prepare_tables(im.src_bf16, im.q0, c.tab_k[1], c.tab_q[1], tables, cx.s));
     // second form of the chained attention (msam_tune_set "chain_variant" 9): its prompt-independent tables in front of `tables`,
     // the per-prompt M fragments behind the layer-0 operands
     const bool chain2 = chain && g_tune_chain_variant == 9;
     void* const tables2 = (char*)tables - msam_chain_tables2_bytes();
     void* const mfrag = (char*)oper0 + msam_i2t_fold_operand_bytes(P);
-    if (chain2) CHECK(msam_chain_prepare_tables2_c(im.src_bf16, c.chain2, tables2, cx.s));
+    if (chain2 && !pf_out) CHECK(msam_chain_prepare_tables2_c(im.src_bf16, c.chain2, tables2, cx.s));
     // hand-over (msam_tune_set "chain_handover"): the attention kernel of layer 1 stores the probabilities and LayerNorm statistics of
     // its layer-0 block per tile in w.hand, the stream kernel at the end of layer 1 reads them instead of computing them again.  Both
     // run on this stream, the token side of layer 1 between them: no other buffer of the workspace is free over that span
     const bool handover = chain2 && g_tune_chain_handover != 0;
+    // merged groups: products that read the same operands go out in one grouped launch (see step 4).  The k / v of layer 1's self attention
+    // wait in w.tmp, which is free between norm3 of layer 0 and the out projection behind that self attention
+    const bool merge = !dbg;
+    u16* const ks_1 = (u16*)w.tmp; u16* const vs_1 = ks_1 + (long)M * C;
     for (int li = 0; li < nlayers && li < 2; ++li) {
         const msam_twoway_layer_t& L = dec->layer[li];
         // (1) token self attention
-        // layer 0: q = k = v input = bf16(tokens), written by prompt_tokens_kernel; layer 1: q = k input carries the PE
-        const u16* sv = w.a;
-        if (li > 0) {
-            // (w.a, w.b) = round16(queries + pe), round16(queries): written behind norm3 of the previous layer (step 3) and still
-            // valid - step 4 only reads them and updates the image-token stream
-            if (!fuse_tok) ADD_CAST2(w.queries, w.qpe, w.a, w.b);
-            sv = w.b;
-        }
-        {
+        // layer 1 (merged form): (w.a, w.b) = round16(queries + pe), round16(queries) were written behind norm3 of layer 0 (step 3) and are
+        // still valid - step 4 only reads them and updates the image-token stream -, and its q / k / v went out with layer 0's step 4
+        const bool have_qkv = li > 0 && merge;
+        // with a block the whole of step (1) and the q of step (2) are the block's
+        const bool have_prefix = li == 0 && pf_in != nullptr;
+        u16* const ks_s = have_qkv ? ks_1 : w.ks; u16* const vs_s = have_qkv ? vs_1 : w.vs;
+        if (!have_qkv && !have_prefix) {
+            // layer 0: q = k = v input = bf16(tokens), written by prompt_tokens_kernel; layer 1: q = k input carries the PE
+            const u16* sv = li > 0 ? w.b : w.a;
             const msam_gemm_t qkv[3] = {mk_gemm(w.a, C, L.self_attn.q_w, M, C, C, L.self_attn.q_b, w.qs, MSAM_D16, C),
                                         mk_gemm(w.a, C, L.self_attn.k_w, M, C, C, L.self_attn.k_b, w.ks, MSAM_D16, C),
                                         mk_gemm(sv, C, L.self_attn.v_w, M, C, C, L.self_attn.v_b, w.vs, MSAM_D16, C)};
             CHECK(msam_gemm_group_bf16(qkv, 3, cx.s));
         }
-        hipLaunchKernelGGL(token_self_attn_kernel, dim3(P), dim3(128), 0, cx.s, w.qs, w.ks, w.vs, Nt, w.attn_tok);
+        // layer 0's norm1 output and the q of its token->image attention: see q_n1 / qs_0 above
+        float* const n1_out = li == 0 ? q_n1 : w.queries;
+        const float* const n1_res = have_prefix ? pf_in->queries : n1_out;       // the residual of step (2)
+        const u16* const qs_l = have_prefix ? pf_in->q : (li == 0 ? qs_0 : w.qs);
+        if (!have_prefix) {
+        hipLaunchKernelGGL(token_self_attn_kernel, dim3(P), dim3(128), 0, cx.s, w.qs, ks_s, vs_s, Nt, w.attn_tok);
         CHECK(msam_check_launch("token_self_attn"));
         if (fuse_tok) {
             CHECK(gemm_ln_tok(cx, w.attn_tok, C, L.self_attn.o_w, M, C, L.self_attn.o_b, li == 0 ? nullptr : w.queries, L.n1_w, L.n1_b,
-                              w.queries, w.qpe, w.a, nullptr));
+                              n1_out, w.qpe, w.a, nullptr));
         } else {
         CHECK(gemm(cx, w.attn_tok, C, L.self_attn.o_w, M, C, C, L.self_attn.o_b, w.tmp, MSAM_F32, C, 0,
                    li == 0 ? nullptr : w.queries, li == 0 ? 0 : MSAM_F32, C));
-        LN(w.tmp, L.n1_w, L.n1_b, M, w.queries, MSAM_F32);
+        LN(w.tmp, L.n1_w, L.n1_b, M, n1_out, MSAM_F32);
         // (2) token -> image attention
-        ADD_CAST(w.queries, w.qpe, w.a);
+        ADD_CAST(n1_out, w.qpe, w.a);
         }
-        CHECK(gemm(cx, w.a, C, L.t2i.q_w, M, CI, C, L.t2i.q_b, w.qs, MSAM_D16, CI));
+        CHECK(gemm(cx, w.a, C, L.t2i.q_w, M, CI, C, L.t2i.q_b, (u16*)qs_l, MSAM_D16, CI));
+        }
+        if (pf_out) return 0;                        // the block is complete
         if (li == 0 && !own_src) {
             // prompt-independent K / V^T of the shared embedding (prepare_image): 1 MiB, L2 resident
-            if (Nt <= 8)
-                hipLaunchKernelGGL(t2i_shared4_kernel, dim3(((P + 3) / 4) * 8), dim3(256), 0, cx.s, w.qs, im.k0, im.vT0, P, Nt,
-                                   w.attn_tok);
-            else
-                hipLaunchKernelGGL(t2i_attn_kernel, dim3(P * 8), dim3(256), 0, cx.s, w.qs, im.k0, im.vT0, 1, Nt, w.attn_tok);
+            if (Nt <= 8) {
+                const int G = g_tune_t2i_shared_group == 16 ? 16 : (g_tune_t2i_shared_group == 8 ? 8 : 4);
+                const dim3 grid(((P + G - 1) / G) * 8);
+                if (G == 4) hipLaunchKernelGGL(t2i_shared_kernel<4>, grid, dim3(256), 0, cx.s, qs_l, im.k0, im.vT0, P, Nt, w.attn_tok);
+                else if (G == 8) hipLaunchKernelGGL(t2i_shared_kernel<8>, grid, dim3(256), 0, cx.s, qs_l, im.k0, im.vT0, P, Nt, w.attn_tok);
+                else hipLaunchKernelGGL(t2i_shared_kernel<16>, grid, dim3(256), 0, cx.s, qs_l, im.k0, im.vT0, P, Nt, w.attn_tok);
+            } else {
+                hipLaunchKernelGGL(t2i_attn_kernel, dim3(P * 8), dim3(256), 0, cx.s, qs_l, im.k0, im.vT0, 1, Nt, w.attn_tok);
+            }
             CHECK(msam_check_launch("t2i_attn"));
         } else if (chain) {
             const msam_twoway_layer_t& L0 = dec->layer[0];
@@ -883,12 +977,12 @@ int decoder_run(const msam_decoder_t* dec, const msam_mask_prompt_t* mask_w, con
                 CHECK(msam_i2t0_t2i_fused(tables, oper0, L0.n4_w, L0.n4_b, 1e-5f, w.qs, P, Nt, L.t2i.k_w, L.t2i.v_w, L.t2i.v_b,
                                           w.attn_tok, w.vT, avail, cx.s));
         } else {
-            CHECK(t2i_stream(cx, w, c, li, L.t2i, P, Nt));
+            CHECK(t2i_stream(cx, w, c, li, L.t2i, P, Nt, false, qs_l));
         }
         if (fuse_tok) {
-            CHECK(gemm_ln_tok(cx, w.attn_tok, CI, L.t2i.o_w, M, CI, L.t2i.o_b, w.queries, L.n2_w, L.n2_b, w.queries, nullptr, w.a, nullptr));
+            CHECK(gemm_ln_tok(cx, w.attn_tok, CI, L.t2i.o_w, M, CI, L.t2i.o_b, n1_res, L.n2_w, L.n2_b, w.queries, nullptr, w.a, nullptr));
         } else {
-        CHECK(gemm(cx, w.attn_tok, CI, L.t2i.o_w, M, C, CI, L.t2i.o_b, w.tmp, MSAM_F32, C, 0, w.queries, MSAM_F32, C));
+        CHECK(gemm(cx, w.attn_tok, CI, L.t2i.o_w, M, C, CI, L.t2i.o_b, w.tmp, MSAM_F32, C, 0, n1_res, MSAM_F32, C));
         LN(w.tmp, L.n2_w, L.n2_b, M, w.queries, MSAM_F32);
         // (3) token MLP (mlp_split reads the fp32 LayerNorm output itself: no plain 16-bit copy needed)
         if (!(L.mlp1_ws != nullptr && L.mlp2_ws != nullptr)) ADD_CAST(w.queries, nullptr, w.a);
@@ -926,9 +1020,20 @@ int decoder_run(const msam_decoder_t* dec, const msam_mask_prompt_t* mask_w, con
         ADD_CAST2(w.queries, w.qpe, w.a, w.b);
         }
         {
-            const msam_gemm_t kv[2] = {mk_gemm(w.a, C, L.i2t.k_w, M, CI, C, L.i2t.k_b, w.ks, MSAM_D16, CI),
-                                       mk_gemm(w.b, C, L.i2t.v_w, M, CI, C, L.i2t.v_b, w.vs, MSAM_D16, CI)};
-            CHECK(msam_gemm_group_bf16(kv, 2, cx.s));
+            // with the k | v of this attention go the products that read the same (w.a, w.b) next: behind layer 0 the q / k / v of layer 1's
+            // self attention, behind layer 1 the q of the final attention (w.qs is free from this layer's token->image kernel onwards)
+            msam_gemm_t kv[5] = {mk_gemm(w.a, C, L.i2t.k_w, M, CI, C, L.i2t.k_b, w.ks, MSAM_D16, CI),
+                                 mk_gemm(w.b, C, L.i2t.v_w, M, CI, C, L.i2t.v_b, w.vs, MSAM_D16, CI)};
+            int nkv = 2;
+            if (merge && li == 0) {
+                const msam_attn_w_t& S = dec->layer[1].self_attn;
+                kv[nkv++] = mk_gemm(w.a, C, S.q_w, M, C, C, S.q_b, w.qs, MSAM_D16, C);
+                kv[nkv++] = mk_gemm(w.a, C, S.k_w, M, C, C, S.k_b, ks_1, MSAM_D16, C);
+                kv[nkv++] = mk_gemm(w.b, C, S.v_w, M, C, C, S.v_b, vs_1, MSAM_D16, C);
+            } else if (merge) {
+                kv[nkv++] = mk_gemm(w.a, C, dec->final_attn.q_w, M, CI, C, dec->final_attn.q_b, w.qs, MSAM_D16, CI);
+            }
+            CHECK(msam_gemm_group_bf16(kv, nkv, cx.s));
         }
         // image->token attention + out_proj + residual + norm4 in ONE pass over the stream: folded form (decfold.hip)
         // for up to 8 tokens per prompt, weights-stationary fused kernel (declayer.hip) otherwise
@@ -959,10 +1064,8 @@ int decoder_run(const msam_decoder_t* dec, const msam_mask_prompt_t* mask_w, con
         }
     }
     if (dbg) return 0;   // test hook: leave queries / keys of the last executed layer in the workspace
-    // final token -> image attention
-    if (!fuse_tok) ADD_CAST(w.queries, w.qpe, w.a);          // (fused form: w.a = round16(queries + pe) already, see above)
-    CHECK(gemm(cx, w.a, C, dec->final_attn.q_w, M, CI, C, dec->final_attn.q_b, w.qs, MSAM_D16, CI));
-    CHECK(t2i_stream(cx, w, c, 2, dec->final_attn, P, Nt, chain));
+    // final token -> image attention: its q = (queries + pe) Wq^T went out with layer 1's step 4 (w.a = round16(queries + pe) since norm3)
+    CHECK(t2i_stream(cx, w, c, 2, dec->final_attn, P, Nt, chain, w.qs));
     if (fuse_tok) {
         CHECK(gemm_ln_tok(cx, w.attn_tok, CI, dec->final_attn.o_w, M, CI, dec->final_attn.o_b, w.queries, dec->nf_w, dec->nf_b, w.queries,
                           nullptr, w.a, nullptr));

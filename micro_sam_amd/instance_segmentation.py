@@ -25,7 +25,8 @@ from typing import Any, Dict, List, Optional, Union
 import numpy as np
 import torch
 
-from . import amg_utils, ops, util
+from . import _lib, amg_utils, ops, util
+from ._prompt_prefix import PromptPrefixCache
 from .predictor import SamPredictor
 
 
@@ -343,7 +344,7 @@ class AutomaticMaskGenerator(AMGBase):
         import copy
         clone = copy.copy(self)
         clone._predictor = lane_predictor if lane_predictor is not None else SamPredictor(self._predictor.model.lane_view())
-        clone._prompt_cache = {}
+        clone._prompt_cache = PromptPrefixCache()
         clone._lanes = clone._post_stream = None
         clone.clear_state()
         return clone
@@ -388,23 +389,35 @@ class AutomaticMaskGenerator(AMGBase):
 
     def _process_batch(self, points, im_size, crop_box, original_size):
         # the grid prompts of a crop size are the same for every image: keep their device copy (one H2D copy and one fill
-        # less per tile - each is a separate, serialising command on the stream)
-        key = (points.shape, tuple(im_size), float(points[0, 0]), float(points[-1, -1]))
-        cached = self._prompt_cache.get(key) if hasattr(self, "_prompt_cache") else None
-        if cached is None or cached[0].device != self._predictor.device or not np.array_equal(cached[2], points):
-            transformed_points = self._predictor.transform.apply_coords(points, im_size)
-            in_points = torch.as_tensor(transformed_points, device=self._predictor.device, dtype=torch.float)
+        # less per tile - each is a separate, serialising command on the stream) and, on the kernel path, the part of the
+        # decode that reads nothing else (Sam.make_prompt_prefix: 7 launches less per tile).  The knob is read HERE, once per
+        # call (msam_tune_set("prompt_prefix", 0): no block is kept and every decode runs those launches itself)
+        predictor = self._predictor
+        model = predictor.model
+        with_prefix = not model.reference_formulation and _lib.tune_get("prompt_prefix") == 1
+        # the blocks belong to the decoder's prepared constants: another object (new weights, settings, a PEFT merge) drops them all
+        owner = model._prepare_decoder() if with_prefix else None
+        device = predictor.device
+
+        def make(pts_host):
+            transformed_points = predictor.transform.apply_coords(pts_host, im_size)
+            in_points = torch.as_tensor(transformed_points, device=device, dtype=torch.float)
             in_labels = torch.ones(in_points.shape[0], dtype=torch.int, device=in_points.device)
-            if not hasattr(self, "_prompt_cache"):
-                self._prompt_cache = {}
-            if len(self._prompt_cache) > 64:
-                self._prompt_cache.clear()
-            self._prompt_cache[key] = (in_points, in_labels, np.array(points, copy=True))
+            prefix = model.make_prompt_prefix(in_points[:, None, :], in_labels[:, None]) if with_prefix else None
+            return in_points, in_labels, prefix
+
+        if getattr(self, "_prompt_cache", None) is None:
+            self._prompt_cache = PromptPrefixCache()
+        key = (points.shape, tuple(im_size), float(points[0, 0]), float(points[-1, -1]), str(device), with_prefix)
+        in_points, in_labels, prefix = self._prompt_cache.get(key, points, owner, make)
+        if prefix is not None:
+            iou_preds, post = predictor.predict_masks_device(None, None, multimask_output=True,
+                                                             stability_score_offset=self._stability_score_offset,
+                                                             prompt_prefix=prefix)
         else:
-            in_points, in_labels = cached[0], cached[1]
-        iou_preds, post = self._predictor.predict_masks_device(
-            in_points[:, None, :], in_labels[:, None], multimask_output=True,
-            stability_score_offset=self._stability_score_offset)
+            iou_preds, post = predictor.predict_masks_device(
+                in_points[:, None, :], in_labels[:, None], multimask_output=True,
+                stability_score_offset=self._stability_score_offset)
         return self._to_mask_data_device(iou_preds, post, crop_box, original_size, points=points)
 
     def _process_crop(self, image, crop_box, crop_layer_idx, precomputed_embeddings, pbar_init=None, pbar_update=None):

@@ -770,10 +770,41 @@ class Sam(nn.Module):
         return low, iou
 
     @torch.no_grad()
+    def make_prompt_prefix(self, point_coords: Optional[torch.Tensor], point_labels: Optional[torch.Tensor],
+                           boxes: Optional[torch.Tensor] = None) -> "PromptPrefix":
+        """The part of ``decode`` that reads the prompts and the decoder weights only (``msam_decoder_prompt_prefix``), for prompts
+        that stay the same from image to image.  ``decode(features, None, None, prompt_prefix=...)`` then skips it and returns the
+        same bits.  The result belongs to this model's prepared decoder constants: after new weights, ``set_split_token_mlp`` or a
+        PEFT merge ``decode`` refuses it.  Kernel path only (not ``set_precision("strict" / "split16")``)."""
+        if self.reference_formulation:
+            raise ValueError("micro_sam_amd: a prompt prefix belongs to the kernel path (precision 'default')")
+        if point_coords is None and boxes is None:
+            raise ValueError("micro_sam_amd: a prompt prefix needs points and / or boxes")
+        prepared = self._prepare_decoder()
+        p = prepared[0]
+        lib = _lib.load()
+        dev = self.device
+        pts = lbl = None
+        if point_coords is not None:
+            pts = point_coords.to(device=dev, dtype=torch.float32).contiguous()
+            lbl = point_labels.to(device=dev, dtype=torch.int32).contiguous()
+            P, Np = pts.shape[0], pts.shape[1]
+        else:
+            P, Np = boxes.reshape(-1, 4).shape[0], 0
+        bx = None if boxes is None else boxes.to(device=dev, dtype=torch.float32).reshape(-1, 4).contiguous()
+        Nt = 5 + Np + (2 if bx is not None else (1 if Np > 0 else 0))
+        block = torch.empty(lib.msam_decoder_prompt_prefix_bytes(P, Nt), dtype=torch.uint8, device=dev)
+        ws = self._workspace(P)
+        _lib.check(lib.msam_decoder_prompt_prefix(C.byref(p), _lib.ptr(pts), _lib.ptr(lbl), Np, _lib.ptr(bx), P, block.data_ptr(),
+                                                  ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "msam_decoder_prompt_prefix")
+        return PromptPrefix(block, pts, lbl, bx, prepared)
+
+    @torch.no_grad()
     def decode(self, features: torch.Tensor, point_coords: Optional[torch.Tensor], point_labels: Optional[torch.Tensor],
                boxes: Optional[torch.Tensor] = None, mask_input: Optional[torch.Tensor] = None,
                multimask_output: bool = True, low_res_dtype: torch.dtype = torch.float32,
-               range_map: Union[bool, torch.Tensor] = False) -> Tuple[torch.Tensor, ...]:
+               range_map: Union[bool, torch.Tensor] = False,
+               prompt_prefix: Optional["PromptPrefix"] = None) -> Tuple[torch.Tensor, ...]:
         """prompt_encoder + mask_decoder of ``SamPredictor.predict_torch`` for one image embedding [1,256,64,64].
 
         point_coords [P,Np,2] / boxes [P,4] are in the 1024 input frame.  Returns (low_res [P,C,256,256], iou [P,C]).
@@ -782,7 +813,15 @@ class Sam(nn.Module):
         ``range_map`` (fp32 logits of the kernel path, no mask prompt): True, or a float32 device tensor [P,C,256,4,2] to fill - the
         up-scaling kernel also writes the {min, max} of every 64-pixel segment of every low-res row, and the map is returned as a
         third value (``ops.postprocess_masks(range_map=...)`` reads it first).  The map is written whenever it is asked for; whether to
-        ask is the caller's decision (``SamPredictor.predict_masks_device`` reads ``msam_tune_set("amg_range_map", ...)`` for it)."""
+        ask is the caller's decision (``SamPredictor.predict_masks_device`` reads ``msam_tune_set("amg_range_map", ...)`` for it).
+        ``prompt_prefix`` (``make_prompt_prefix``): the points, labels and boxes are the prefix's own (pass None for them) and the
+        launches it stands for are skipped; a mask input may still come with it."""
+        if prompt_prefix is not None:
+            if self.reference_formulation:
+                raise ValueError("micro_sam_amd: a prompt prefix belongs to the kernel path (precision 'default')")
+            if point_coords is not None or point_labels is not None or boxes is not None:
+                raise ValueError("micro_sam_amd: with a prompt prefix the points, labels and boxes are the prefix's own")
+            point_coords, point_labels, boxes = prompt_prefix.points, prompt_prefix.labels, prompt_prefix.boxes
         want_range = range_map is not False and range_map is not None
         if want_range and (low_res_dtype != torch.float32 or self.reference_formulation or mask_input is not None):
             raise ValueError("range_map goes with float32 low-res logits of the kernel path, without a mask prompt")
@@ -800,6 +839,9 @@ class Sam(nn.Module):
             return (low if low_res_dtype == torch.float32 else low.to(low_res_dtype)), iou
         prepared = self._prepare_decoder()
         p, _, consts = prepared
+        if prompt_prefix is not None and (prompt_prefix.prepared is not prepared or prompt_prefix.block.device != self.device):
+            raise ValueError("micro_sam_amd: the prompt prefix was made for other decoder constants (new weights or settings) or "
+                             "another device; make it again")
         state = self._image_state(features, prepared)
         lib = _lib.load()
         dev = self.device
@@ -834,13 +876,28 @@ class Sam(nn.Module):
             msk = mask_input.to(device=dev, dtype=torch.float32).reshape(-1, 4 * GRID, 4 * GRID).contiguous()
             if msk.shape[0] != P:
                 raise ValueError(f"mask_input holds {msk.shape[0]} masks for {P} prompts")
-        _lib.check(lib.msam_decoder_forward_masks(
-            C.byref(p), C.byref(self._mask_params), consts.data_ptr(), state.data_ptr(), _lib.ptr(pts), _lib.ptr(lbl), Np,
-            _lib.ptr(bx), _lib.ptr(msk), P, 1 if multimask_output else 0, low.data_ptr(), iou.data_ptr(),
-            self._dec_ws.data_ptr(), self._dec_ws.numel(), _lib.stream_ptr()), "msam_decoder_forward")
+        if prompt_prefix is not None:
+            _lib.check(lib.msam_decoder_forward_masks_prefixed(
+                C.byref(p), C.byref(self._mask_params), consts.data_ptr(), state.data_ptr(), _lib.ptr(pts), _lib.ptr(lbl), Np,
+                _lib.ptr(bx), _lib.ptr(msk), prompt_prefix.block.data_ptr(), P, 1 if multimask_output else 0, low.data_ptr(),
+                iou.data_ptr(), self._dec_ws.data_ptr(), self._dec_ws.numel(), _lib.stream_ptr()), "msam_decoder_forward")
+        else:
+            _lib.check(lib.msam_decoder_forward_masks(
+                C.byref(p), C.byref(self._mask_params), consts.data_ptr(), state.data_ptr(), _lib.ptr(pts), _lib.ptr(lbl), Np,
+                _lib.ptr(bx), _lib.ptr(msk), P, 1 if multimask_output else 0, low.data_ptr(), iou.data_ptr(),
+                self._dec_ws.data_ptr(), self._dec_ws.numel(), _lib.stream_ptr()), "msam_decoder_forward")
         if want_range:
             return low, iou, rng
         return low, iou
+
+
+class PromptPrefix:
+    """What ``Sam.make_prompt_prefix`` leaves on the device: the block of ``msam_decoder_prompt_prefix`` (read-only for every decode),
+    the prompt tensors it was computed from, and the prepared decoder constants it belongs to."""
+    __slots__ = ("block", "points", "labels", "boxes", "prepared")
+
+    def __init__(self, block, points, labels, boxes, prepared):
+        self.block, self.points, self.labels, self.boxes, self.prepared = block, points, labels, boxes, prepared
 
 
 def build_sam(model_type: str = "vit_b", num_multimask_outputs: int = 3) -> Sam:

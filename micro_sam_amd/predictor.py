@@ -110,10 +110,11 @@ class SamPredictor:
 
     @torch.no_grad()
     def predict_masks_device(self, point_coords, point_labels, boxes=None, multimask_output: bool = True,
-                             stability_score_offset: float = 1.0):
+                             stability_score_offset: float = 1.0, prompt_prefix=None):
         """AMG fast path: decode + fused post-processing without materialising full-resolution logits.
 
-        Returns (iou [B,C], dict(counts, boxes, bits)) - see ops.postprocess_masks."""
+        Returns (iou [B,C], dict(counts, boxes, bits)) - see ops.postprocess_masks.
+        ``prompt_prefix`` (``Sam.make_prompt_prefix``): stands for the prompts; pass None for points, labels and boxes."""
         if not self.is_image_set:
             raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
         # the low-res logits go from the up-scaling kernel to the post-processing kernel (never returned to the caller).  fp32 logits of a
@@ -126,7 +127,7 @@ class SamPredictor:
                     and tuple(int(v) for v in self.input_size) == (1024, 1024)
                     and tuple(int(v) for v in self.original_size) == (1024, 1024) and _lib.tune_get("amg_range_map") == 1)
         out = self.model.decode(self.features, point_coords, point_labels, boxes, None, multimask_output, low_res_dtype=dt,
-                                range_map=with_map)
+                                range_map=with_map, prompt_prefix=prompt_prefix)
         low, iou = out[0], out[1]
         from .ops import postprocess_masks
         b, c = low.shape[:2]
