@@ -972,6 +972,33 @@ int msam_label_props(const int32_t* labels, int32_t H, int32_t W, const int32_t*
 int64_t msam_distance_targets_workspace_bytes(int32_t H, int32_t W, int32_t N);
 int msam_distance_targets(const int32_t* labels, int32_t H, int32_t W, int32_t N, int32_t correct_centers, float fill, float* out,
                           int32_t* center, int32_t* dmax2, int32_t* bbox, void* workspace, int64_t workspace_bytes, void* stream);
+/* Point prompts from the decoder maps: _derive_point_prompts -> _get_centers of the reference's AutomaticPromptGenerator
+ * (micro_sam/instance_segmentation.py:1322-1379), from the three maps to one centre per seed component on the device (DESIGN.md
+ * section 8.11; scikit-image and python-elf are not pinned).  foreground, center_distances, boundary_distances: float32 [H, W],
+ * 1 <= H, W <= 32767.  All integer after the first step, and exact:
+ *   seed       : (center_distances < ct) && (boundary_distances < bt) && !(foreground < ft), each map value widened to fp64 and compared
+ *                with the fp64 threshold (no threshold may be NaN); a NaN map value compares false, so a NaN foreground keeps a seed;
+ *   components : the 4-connected components of the seed image, numbered 1..N by the rank of their first pixel in block-major order
+ *                (512 x 512 blocks): the ascending root keys of msam_label_components;
+ *   zero set Z : find_boundaries(mode="outer") of the component image - a background pixel with an edge neighbour inside the image that
+ *                is an object; an object pixel with a diagonal neighbour inside the image of another component - and, with
+ *                avoid_image_border = 1, every pixel of the first and the last row and column;
+ *   D(p)       : for a component pixel p of 512-block B the exact squared Euclidean distance to the nearest pixel of Z inside B grown by
+ *                16 rows and columns on every side, clipped to the image (elf.parallel.distance_transform(halo=(16, 16),
+ *                block_shape=(512, 512))); 0 on Z;
+ *   centre k   : the component's own pixel with the largest D, among equals the first in raster order; when the largest D is 0, (y0, x0)
+ *                of the component's bounding box (argmax over an all-zero crop), which need not be a pixel of the component.
+ * centers: int32 [max_centers, 2] (y, x), rows 0..min(N, max_centers) - 1 are written, in component order; N <= ceil(H * W / 2).
+ * result: DEVICE int32 [4] = N; 1 when some component pixel's window holds no pixel of Z (the reference's distance is undefined there:
+ * the centres are unspecified); the flag of the labelling (0 = complete, see msam_label_components_async); 0.
+ * workspace: the caller's, 8-byte aligned: 16 bytes per centre + 13 bytes per pixel + int32 [3, ceil(H / 32), W] + int32 [ceil(H * W / 4096)]
+ * (the query returns 0 for bad sides or max_centers < 1).  Integer atomics whose result does not depend on their order: two calls agree
+ * bit for bit.  Kernels on `stream`, no synchronisation, nothing read back. */
+int64_t msam_seed_centers_workspace_bytes(int32_t H, int32_t W, int32_t max_centers);
+int msam_seed_centers(const float* foreground, const float* center_distances, const float* boundary_distances, int32_t H, int32_t W,
+                      double foreground_threshold, double center_distance_threshold, double boundary_distance_threshold,
+                      int32_t avoid_image_border, int32_t* centers, int32_t max_centers, int32_t* result, void* workspace,
+                      int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Slice-to-slice propagation of P objects at once (multi_dimensional_segmentation.segment_objects_in_volume; reference

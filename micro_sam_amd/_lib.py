@@ -270,6 +270,8 @@ _PROTOS = {
     "msam_label_props": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "msam_distance_targets_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "msam_distance_targets": (_i32, [_vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "msam_seed_centers_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "msam_seed_centers": (_i32, [_vp, _vp, _vp, _i32, _i32, C.c_double, C.c_double, C.c_double, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
     "msam_mask_pack": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "msam_mask_iou_counts": (_i32, [_vp, _vp, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp]),
     "msam_mask_box_prompts": (_i32, [_vp, _i32, _i32, _i32, C.c_double, _i32, _i32, _vp, _vp, _vp]),

@@ -21,6 +21,17 @@
 // passes towards labels 1..N: the zero pixels are scikit-image's find_boundaries(mode="inner") - only neighbours INSIDE the image count -,
 // the object index is the label itself, and one pixel-parallel pass writes the foreground, centre-distance and boundary-distance planes
 // from a 16-byte record per object.
+//
+// msam_seed_centers (the first stage of AutomaticPromptGenerator.generate: _derive_point_prompts -> _get_centers, reference
+// micro_sam/instance_segmentation.py:1322-1379) runs from the three decoder maps to one point per seed component without a host pass:
+//   seeds    : (c < ct) && (b < bt) && !(f < ft) per pixel, compared in fp64
+//   label    : msam_label_components_async (segment.hip): per pixel the block-major key of its component's first pixel
+//   interior : one byte per pixel, 0 on the zero set Z = find_boundaries(mode="outer") of the component image (+ the image border)
+//   rank     : the roots in ascending key order get 1..N (per 4096 keys: count, one scan of the counts, ballot ranks)
+//   column   : the passes above on `interior`, with a carry pass that starts anew in every row of 512 x 512 blocks and looks 16 rows
+//              beyond it - elf.parallel.distance_transform(halo=(16, 16), block_shape=(512, 512)) computes every block on its own
+//   row      : as above inside the block's 16-column halo, on component pixels only; one 64-bit atomic maximum per pixel of
+//              (d2 << 32 | ~raster index) selects the largest distance and, among equals, the first pixel in raster order
 #include "common.h"
 #include "../../include/msam_hip.h"
 
@@ -472,4 +483,271 @@ extern "C" int msam_distance_targets(const int32_t* labels, int32_t H, int32_t W
         hipLaunchKernelGGL((dt_write_kernel<1>), dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, s, labels, (const int*)dist, (unsigned)npx,
                            (unsigned)W, N, tab, fill, out);
     return msam_check_launch("msam_distance_targets");
+}
+
+// ---- msam_seed_centers
+namespace {
+
+constexpr int SC_BLOCK = 512, SC_HALO = 16;                            // block_shape and halo of elf.parallel.distance_transform
+constexpr int SC_KEYS = 4096;                                          // keys per workgroup of the ranking (16 rounds of 256)
+static_assert(SC_BLOCK % EDT_SEG == 0 && SC_BLOCK % EDT_TILE == 0, "segments and row tiles nest inside the 512 x 512 blocks");
+
+// NaN compares false on every side, as in numpy: a NaN foreground keeps a seed, a NaN distance drops it
+__global__ __launch_bounds__(256) void sc_seed_kernel(const float* __restrict__ f, const float* __restrict__ c, const float* __restrict__ b,
+                                                      int npx, double ft, double ct, double bt, int* __restrict__ seeds) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= npx) return;
+    seeds[p] = ((double)c[p] < ct && (double)b[p] < bt && !((double)f[p] < ft)) ? 1 : 0;
+}
+
+// interior[p] = 0 on the zero set Z of the distance transform, 1 elsewhere.  Z = find_boundaries(mode="outer") of the component image:
+//   background pixel: an edge neighbour inside the image is an object;
+//   object pixel    : scikit-image asks for an edge neighbour of another value AND a different object in the 8-neighbourhood.  The
+//                     objects are the 4-connected components of a binary image, so an object edge neighbour is of the same component:
+//                     a different object can only sit on a diagonal.  If the diagonal neighbour q of p is of another component, the
+//                     two pixels that share an edge with both p and q (inside the image, since they lie between p and q) are
+//                     background, or they would join p and q - so p has an edge neighbour of another value as well.  The rule
+//                     therefore is: a diagonal neighbour inside the image belongs to another component;
+//   avoid_border    : every pixel of the first and the last row and column.
+__global__ __launch_bounds__(256) void sc_interior_kernel(const int* __restrict__ roots, int H, int W, int avoid_border,
+                                                          unsigned char* __restrict__ interior) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= W) return;
+    const size_t p = (size_t)y * W + x;
+    const bool up = y > 0, down = y + 1 < H, left = x > 0, right = x + 1 < W;
+    const int r = roots[p];
+    bool zero;
+    if (avoid_border && !(up && down && left && right)) zero = true;
+    else if (r < 0) zero = (up && roots[p - W] >= 0) || (down && roots[p + W] >= 0) || (left && roots[p - 1] >= 0) || (right && roots[p + 1] >= 0);
+    else {
+        auto other = [&](int v) { return v >= 0 && v != r; };
+        zero = (up && left && other(roots[p - W - 1])) || (up && right && other(roots[p - W + 1])) ||
+               (down && left && other(roots[p + W - 1])) || (down && right && other(roots[p + W + 1]));
+    }
+    interior[p] = zero ? 0 : 1;
+}
+
+// key k is a root when the pixel it names holds k
+MSAM_DEVINL bool sc_is_root(const int* __restrict__ roots, int k, int npx, int H, int W) { return k < npx && roots[bm_pix(k, H, W)] == k; }
+
+__global__ __launch_bounds__(256) void sc_count_kernel(const int* __restrict__ roots, int H, int W, int npx, int* __restrict__ counts) {
+    __shared__ int part[4];
+    const int k0 = blockIdx.x * SC_KEYS + threadIdx.x;
+    int cnt = 0;
+    for (int i = 0; i < SC_KEYS / 256; ++i) cnt += __popcll(__ballot(sc_is_root(roots, k0 + i * 256, npx, H, W)));     // the wave's count
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+// one workgroup: counts -> exclusive prefix sums in place; result = {N, 0 (the "undefined" flag), (the labelling's flag: untouched), 0}
+__global__ __launch_bounds__(256) void sc_scan_kernel(int* __restrict__ counts, int nblk, int* __restrict__ result) {
+    __shared__ int part[256];
+    const int per = (nblk + 255) / 256, i0 = threadIdx.x * per, i1 = i0 + per < nblk ? i0 + per : nblk;
+    int sum = 0;
+    for (int i = i0; i < i1; ++i) sum += counts[i];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0;
+        for (int t = 0; t < 256; ++t) { const int v = part[t]; part[t] = run; run += v; }
+        result[0] = run; result[1] = 0; result[3] = 0;
+    }
+    __syncthreads();
+    int run = part[threadIdx.x];
+    for (int i = i0; i < i1; ++i) { const int v = counts[i]; counts[i] = run; run += v; }
+}
+
+// rank[k] = 0-based rank of root key k among the roots; the records of the components below `cap` are cleared here
+__global__ __launch_bounds__(256) void sc_rank_kernel(const int* __restrict__ roots, int H, int W, int npx, const int* __restrict__ offsets,
+                                                      int cap, int* __restrict__ rank, u64* __restrict__ best, int* __restrict__ corner) {
+    constexpr int R = SC_KEYS / 256;
+    __shared__ int tot[R * 4];
+    const int k0 = blockIdx.x * SC_KEYS + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned mine = 0;                                                  // bit i: this thread's key of round i is a root
+    int before[R];                                                      // roots of the same wave and round at lower lanes
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        const bool is = sc_is_root(roots, k0 + i * 256, npx, H, W);
+        const u64 bal = __ballot(is);
+        mine |= is ? 1u << i : 0u;
+        before[i] = __popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) tot[i * 4 + wave] = __popcll(bal);
+    }
+    __syncthreads();
+    if (!mine) return;
+    int run = offsets[blockIdx.x];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {                                       // keys grow with (round, wave, lane)
+        for (int w = 0; w < 4; ++w) {
+            if (w == wave && ((mine >> i) & 1u)) {
+                const int o = run + before[i];
+                rank[k0 + i * 256] = o;
+                if (o < cap) { best[o] = 0; corner[2 * o] = LP_NONE; corner[2 * o + 1] = LP_NONE; }
+            }
+            run += tot[i * 4 + w];
+        }
+    }
+}
+
+// the carry pass of the column sweeps, per (column, row of 512 x 512 blocks): the distances carried into the block's segments start
+// from the 16 rows above and below the block and never cross them
+__global__ __launch_bounds__(64) void sc_carry_kernel(const unsigned char* __restrict__ interior, int H, int W, const int* __restrict__ top,
+                                                      int* __restrict__ bot, int* __restrict__ above) {
+    const int x = blockIdx.x * 64 + threadIdx.x;
+    if (x >= W) return;
+    const int y0 = blockIdx.y * SC_BLOCK, y1 = y0 + SC_BLOCK < H ? y0 + SC_BLOCK : H;
+    const int s0 = y0 / EDT_SEG, s1 = (y1 + EDT_SEG - 1) / EDT_SEG;
+    int c = EDT_GINF;
+    for (int d = 1; d <= SC_HALO && y0 - d >= 0; ++d)
+        if (interior[(size_t)(y0 - d) * W + x] == 0) { c = d; break; }
+    for (int s = s0; s < s1; ++s) {
+        const int len = (s + 1) * EDT_SEG <= H ? EDT_SEG : H - s * EDT_SEG;
+        const int b = bot[(size_t)s * W + x];
+        above[(size_t)s * W + x] = c;
+        c = b != EDT_GINF ? b + 1 : (c == EDT_GINF ? EDT_GINF : c + len);
+    }
+    c = EDT_GINF;
+    for (int d = 0; d < SC_HALO && y1 + d < H; ++d)
+        if (interior[(size_t)(y1 + d) * W + x] == 0) { c = d + 1; break; }
+    for (int s = s1 - 1; s >= s0; --s) {
+        const int len = (s + 1) * EDT_SEG <= H ? EDT_SEG : H - s * EDT_SEG;
+        const int t = top[(size_t)s * W + x];
+        bot[(size_t)s * W + x] = c;
+        c = t != EDT_GINF ? t + 1 : (c == EDT_GINF ? EDT_GINF : c + len);
+    }
+}
+
+// *p = max(*p, v): a compare-and-swap loop that most calls leave after the first read (the record only grows)
+MSAM_DEVINL void sc_atomic_max64(u64* p, u64 v) {
+    u64 old = *(volatile u64*)p;
+    while (old < v) {
+        const u64 seen = atomicCAS(p, old, v);
+        if (seen == old) break;
+        old = seen;
+    }
+}
+
+// edt_row_kernel inside the window of the pixel's block (its columns grown by 16, clipped to the image), on component pixels only; the
+// squared distance goes straight into the component's record.  A tile of 256 pixels lies inside one block.
+__global__ __launch_bounds__(256) void sc_row_kernel(const int* __restrict__ g, const int* __restrict__ roots, const int* __restrict__ rank,
+                                                     int W, int cap, u64* __restrict__ best, int* __restrict__ corner, int* __restrict__ result) {
+    __shared__ int sg[EDT_TILE + 2 * EDT_HALO];
+    const int y = blockIdx.y, x0 = blockIdx.x * EDT_TILE;
+    const int bx0 = x0 / SC_BLOCK * SC_BLOCK;
+    const int wlo = bx0 - SC_HALO > 0 ? bx0 - SC_HALO : 0, whi = bx0 + SC_BLOCK + SC_HALO < W ? bx0 + SC_BLOCK + SC_HALO : W;
+    const int* __restrict__ grow = g + (size_t)y * W;
+    for (int i = threadIdx.x; i < EDT_TILE + 2 * EDT_HALO; i += 256) {
+        const int xs = x0 - EDT_HALO + i;
+        sg[i] = (xs >= wlo && xs < whi) ? grow[xs] : EDT_GINF;
+    }
+    __syncthreads();
+    const int x = x0 + threadIdx.x;
+    if (x >= W) return;
+    const unsigned p = (unsigned)y * (unsigned)W + (unsigned)x;         // < 2^30
+    const int r = roots[p];
+    if (r < 0) return;
+    const int c = EDT_HALO + threadIdx.x;
+    const int gc = sg[c];
+    unsigned d2 = gc == EDT_GINF ? EDT_INF : (unsigned)(gc * gc);
+    const int reach = x - wlo > whi - 1 - x ? x - wlo : whi - 1 - x;    // furthest column of the window
+    int dx = 1;
+    for (; dx <= EDT_HALO && dx <= reach && (unsigned)(dx * dx) < d2; ++dx) d2 = edt_take(d2, dx, sg[c - dx], sg[c + dx]);
+    for (; dx <= reach && (unsigned)(dx * dx) < d2; ++dx)               // beyond the staged part of the row
+        d2 = edt_take(d2, dx, x - dx >= wlo ? grow[x - dx] : EDT_GINF, x + dx < whi ? grow[x + dx] : EDT_GINF);
+    if (d2 == EDT_INF) atomicExch(&result[1], 1);                       // no pixel of Z in the window: the reference's value is undefined
+    const int o = rank[r];
+    if (o >= cap) return;
+    sc_atomic_max64(&best[o], ((u64)d2 << 32) | (u64)(0xffffffffu - p));
+    if (d2 == 0) { atomicMin(&corner[2 * o], y); atomicMin(&corner[2 * o + 1], x); }    // read only when every pixel of o holds 0
+}
+
+__global__ __launch_bounds__(256) void sc_finish_kernel(const int* __restrict__ result, int cap, int W, const u64* __restrict__ best,
+                                                        const int* __restrict__ corner, int* __restrict__ centers) {
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o >= cap || o >= result[0]) return;
+    const u64 b = best[o];
+    if ((b >> 32) == 0) {                                               // argmax of an all-zero crop: the corner of the bounding box
+        centers[2 * o] = corner[2 * o]; centers[2 * o + 1] = corner[2 * o + 1];
+    } else {
+        const unsigned p = 0xffffffffu - (unsigned)(b & 0xffffffffull);
+        centers[2 * o] = (int)(p / (unsigned)W); centers[2 * o + 1] = (int)(p % (unsigned)W);
+    }
+}
+
+int64_t sc_blocks(int H, int W) { return ((int64_t)H * W + SC_KEYS - 1) / SC_KEYS; }
+
+}  // namespace
+
+// segment.hip's.  A weak reference: this file still links on its own (the host build of the tests compiles it alone), and
+// msam_seed_centers refuses where the labelling is absent.
+extern "C" __attribute__((weak)) int msam_label_components_async(const int32_t* seg, int32_t H, int32_t W, int32_t* roots, int32_t* changed_flag,
+                                                                 int32_t passes, void* stream);
+
+extern "C" int64_t msam_seed_centers_workspace_bytes(int32_t H, int32_t W, int32_t max_centers) {
+    if (!lp_side_ok(H, W) || max_centers < 1) return 0;
+    // record (64-bit) and corner (two words) per component; seeds / rank, roots, g per pixel; the column pass's carries; the ranking's counts;
+    // one byte per pixel
+    return (int64_t)max_centers * 16 + (int64_t)H * W * 12 + edt_carry_ints(H, W) * 4 + sc_blocks(H, W) * 4 + (int64_t)H * W;
+}
+
+extern "C" int msam_seed_centers(const float* foreground, const float* center_distances, const float* boundary_distances, int32_t H, int32_t W,
+                                 double foreground_threshold, double center_distance_threshold, double boundary_distance_threshold,
+                                 int32_t avoid_image_border, int32_t* centers, int32_t max_centers, int32_t* result, void* workspace,
+                                 int64_t workspace_bytes, void* stream) {
+    if (!foreground || !center_distances || !boundary_distances || !centers || !result || !workspace) {
+        msam_set_error("msam_seed_centers: null pointer");
+        return 1;
+    }
+    if (!lp_side_ok(H, W)) { msam_set_error("msam_seed_centers: 1 <= H, W <= 32767"); return 1; }
+    if (max_centers < 1) { msam_set_error("msam_seed_centers: max_centers >= 1"); return 1; }
+    if (foreground_threshold != foreground_threshold || center_distance_threshold != center_distance_threshold ||
+        boundary_distance_threshold != boundary_distance_threshold) {
+        msam_set_error("msam_seed_centers: a threshold is NaN");
+        return 1;
+    }
+    if (avoid_image_border != 0 && avoid_image_border != 1) { msam_set_error("msam_seed_centers: avoid_image_border must be 0 or 1"); return 1; }
+    if (((uintptr_t)workspace & 7) != 0) { msam_set_error("msam_seed_centers: the workspace must be 8-byte aligned"); return 1; }
+    if (workspace_bytes < msam_seed_centers_workspace_bytes(H, W, max_centers)) {
+        msam_set_error("msam_seed_centers: the workspace is smaller than msam_seed_centers_workspace_bytes says");
+        return 1;
+    }
+    if (!msam_label_components_async) { msam_set_error("msam_seed_centers: this build lacks msam_label_components_async (segment.hip)"); return 1; }
+    hipStream_t s = (hipStream_t)stream;
+    const size_t npx = (size_t)H * W;                                  // <= 32767^2 < 2^30: 32-bit pixel indices and keys
+    const int nblk = (int)sc_blocks(H, W);
+    u64* best = (u64*)workspace;
+    int* corner = (int*)(best + max_centers);
+    int* seeds = corner + 2 * (size_t)max_centers;                     // the rank per root key once the labelling has read the seeds
+    int* roots = seeds + npx;
+    int* g = roots + npx;
+    int* carry = g + npx;
+    int* counts = carry + edt_carry_ints(H, W);
+    unsigned char* interior = (unsigned char*)(counts + nblk);
+    const unsigned pb = (unsigned)((npx + 255) / 256);
+    hipLaunchKernelGGL(sc_seed_kernel, dim3(pb), dim3(256), 0, s, foreground, center_distances, boundary_distances, (int)npx, foreground_threshold,
+                       center_distance_threshold, boundary_distance_threshold, seeds);
+    const int e = msam_label_components_async(seeds, H, W, roots, result + 2, 1, s);     // result[2]: 0 = the labelling is complete
+    if (e) return e;
+    hipLaunchKernelGGL(sc_interior_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0, s, (const int*)roots, H, W,
+                       avoid_image_border, interior);
+    hipLaunchKernelGGL(sc_count_kernel, dim3((unsigned)nblk), dim3(256), 0, s, (const int*)roots, H, W, (int)npx, counts);
+    hipLaunchKernelGGL(sc_scan_kernel, dim3(1), dim3(256), 0, s, counts, nblk, result);
+    int* rank = seeds;
+    hipLaunchKernelGGL(sc_rank_kernel, dim3((unsigned)nblk), dim3(256), 0, s, (const int*)roots, H, W, (int)npx, (const int*)counts, max_centers,
+                       rank, best, corner);
+    const int S = (H + EDT_SEG - 1) / EDT_SEG;
+    int* top = carry;
+    int* bot = top + (size_t)S * W;
+    int* above = bot + (size_t)S * W;
+    const dim3 cols((unsigned)((W + 63) / 64), (unsigned)S);
+    hipLaunchKernelGGL((edt_segment_kernel<SRC_U8>), cols, dim3(64), 0, s, (const void*)interior, H, W, 0, top, bot);
+    hipLaunchKernelGGL(sc_carry_kernel, dim3((unsigned)((W + 63) / 64), (unsigned)((H + SC_BLOCK - 1) / SC_BLOCK)), dim3(64), 0, s,
+                       (const unsigned char*)interior, H, W, (const int*)top, bot, above);
+    hipLaunchKernelGGL((edt_column_kernel<SRC_U8>), cols, dim3(64), 0, s, (const void*)interior, H, W, 0, (const int*)above, (const int*)bot, g);
+    hipLaunchKernelGGL(sc_row_kernel, dim3((unsigned)((W + EDT_TILE - 1) / EDT_TILE), (unsigned)H), dim3(256), 0, s, (const int*)g,
+                       (const int*)roots, (const int*)rank, W, max_centers, best, corner, result);
+    hipLaunchKernelGGL(sc_finish_kernel, dim3((unsigned)(((int64_t)max_centers + 255) / 256)), dim3(256), 0, s, (const int*)result, max_centers, W,
+                       (const u64*)best, (const int*)corner, centers);
+    return msam_check_launch("msam_seed_centers");
 }

@@ -719,6 +719,30 @@ def _derive_point_prompts(foreground: np.ndarray, center_distances: np.ndarray, 
     return {"points": prompts[:, None, ::-1], "point_labels": np.ones((len(prompts), 1))}
 
 
+def _derive_point_prompts_device(foreground, center_distances, boundary_distances, foreground_threshold: float = 0.5,
+                                 center_distance_threshold: float = 0.5, boundary_distance_threshold: float = 0.5):
+    """``_derive_point_prompts`` on the device (``ops.seed_centers``, csrc/labelprops.hip): the same keywords, the same return value,
+    integer for integer.  The maps are device tensors or numpy arrays (uploaded); only the number of components and their centres come
+    back.  Where the reference's blockwise distance transform is undefined (a component that fills a whole 544 x 544 window) the host
+    function answers."""
+    from . import _lib, ops
+    dev = next((m.device for m in (foreground, center_distances, boundary_distances) if torch.is_tensor(m)), None)
+    dev = _lib.require_gpu() if dev is None else dev
+    # float32 maps only (ops.seed_centers refuses anything else): another type would compare differently from the host function
+    maps = [m.contiguous() if torch.is_tensor(m) else torch.from_numpy(np.ascontiguousarray(m)).to(dev)
+            for m in (foreground, center_distances, boundary_distances)]
+    found = ops.seed_centers(*maps, foreground_threshold=foreground_threshold, center_distance_threshold=center_distance_threshold,
+                             boundary_distance_threshold=boundary_distance_threshold)
+    if found.undefined:
+        return _derive_point_prompts(*(m.cpu().numpy() for m in maps), foreground_threshold=foreground_threshold,
+                                     center_distance_threshold=center_distance_threshold,
+                                     boundary_distance_threshold=boundary_distance_threshold)
+    if found.n == 0:
+        return None
+    prompts = found.centers.cpu().numpy().astype(np.int64)
+    return {"points": prompts[:, None, ::-1], "point_labels": np.ones((len(prompts), 1))}
+
+
 def _derive_box_prompts(predictions, box_extension: float):
     """Boxes around the masks of a first round of predictions, grown by ``box_extension`` (reference :1382-1391; the
     clipping against ``shape[0]`` / ``shape[1]`` is the reference's)."""
@@ -791,6 +815,7 @@ class InstanceSegmentationWithDecoder:
         self._predictor = predictor
         self._decoder = decoder
         self._foreground = self._center_distances = self._boundary_distances = None
+        self._device_maps = None                # the decoder output [3, H, W] where it was computed, when that is the device
         self._is_initialized = False
 
     @property
@@ -807,8 +832,10 @@ class InstanceSegmentationWithDecoder:
         self._predictor = util.set_precomputed(self._predictor, image_embeddings, i=i)
         output = self._decoder(self._predictor.features, tuple(self._predictor.input_size),
                                tuple(self._predictor.original_size))
+        device_maps = output.float().squeeze(0).contiguous() if torch.is_tensor(output) and output.is_cuda else None
         output = (output.float().cpu().numpy() if torch.is_tensor(output) else np.asarray(output)).squeeze(0)
         assert output.shape[0] == 3, f"{output.shape}"
+        self._device_maps = device_maps
         pbar_update(1)
         pbar_close()
         self._foreground, self._center_distances, self._boundary_distances = output[0], output[1], output[2]
@@ -862,10 +889,12 @@ class InstanceSegmentationWithDecoder:
         self._foreground = state["foreground"]
         self._center_distances = state["center_distances"]
         self._boundary_distances = state["boundary_distances"]
+        self._device_maps = None
         self._is_initialized = True
 
     def clear_state(self):
         self._foreground = self._center_distances = self._boundary_distances = None
+        self._device_maps = None
         self._is_initialized = False
 
 
@@ -884,22 +913,30 @@ class TiledInstanceSegmentationWithDecoder(InstanceSegmentationWithDecoder):
         tiling = Blocking([0, 0], original_size, tile_shape)
         _, pbar_init, pbar_update, pbar_close = util.handle_pbar(verbose, pbar_init, pbar_update)
         maps = np.zeros((3,) + tuple(original_size), dtype="float32")
+        device_maps, on_device = None, True     # the same stitching on the device, as long as every tile's output arrives there
         tile_ids = list(range(tiling.number_of_blocks)) if tiles_in_mask is None else list(tiles_in_mask)
         pbar_init(len(tile_ids), "Initialize tiled instance segmentation with decoder" + ("" if tiles_in_mask is None else " and mask"))
         for tile_id in tile_ids:
             self._predictor = util.set_precomputed(self._predictor, self._image_embeddings, i=i, tile_id=tile_id)
             output = self._decoder(self._predictor.features, tuple(self._predictor.input_size),
                                    tuple(self._predictor.original_size))
+            device_output = output.float().squeeze(0) if torch.is_tensor(output) and output.is_cuda else None
             output = (output.float().cpu().numpy() if torch.is_tensor(output) else np.asarray(output)).squeeze(0)
             assert output.shape[0] == 3
             block = tiling.get_block_with_halo(tile_id, halo=list(halo))
             local = tuple(slice(b, e) for b, e in zip(block.inner_block_local.begin, block.inner_block_local.end))
             inner = tuple(slice(b, e) for b, e in zip(block.inner_block.begin, block.inner_block.end))
             maps[(slice(None),) + inner] = output[(slice(None),) + local]
+            on_device = on_device and device_output is not None
+            if on_device:
+                if device_maps is None:
+                    device_maps = torch.zeros((3,) + tuple(original_size), dtype=torch.float32, device=device_output.device)
+                device_maps[(slice(None),) + inner] = device_output[(slice(None),) + local]
             pbar_update(1)
         pbar_close()
         self._i = i
         self._foreground, self._center_distances, self._boundary_distances = maps[0], maps[1], maps[2]
+        self._device_maps = device_maps if on_device else None
         self._is_initialized = True
 
 
@@ -917,11 +954,18 @@ class AutomaticPromptGenerator(InstanceSegmentationWithDecoder):
         if not self.is_initialized:
             raise RuntimeError("AutomaticPromptGenerator has not been initialized. Call initialize first.")
         foreground = self._foreground
-        prompt_function = _derive_point_prompts if prompt_function is None else prompt_function
-        prompts = prompt_function(foreground=foreground, center_distances=self._center_distances,
-                                  boundary_distances=self._boundary_distances, foreground_threshold=foreground_threshold,
-                                  center_distance_threshold=center_distance_threshold,
-                                  boundary_distance_threshold=boundary_distance_threshold)
+        device_maps = getattr(self, "_device_maps", None)
+        if prompt_function is None and device_maps is not None:      # the decoder's own output is still on the device: derive there
+            prompts = _derive_point_prompts_device(device_maps[0], device_maps[1], device_maps[2],
+                                                   foreground_threshold=foreground_threshold,
+                                                   center_distance_threshold=center_distance_threshold,
+                                                   boundary_distance_threshold=boundary_distance_threshold)
+        else:
+            prompt_function = _derive_point_prompts if prompt_function is None else prompt_function
+            prompts = prompt_function(foreground=foreground, center_distances=self._center_distances,
+                                      boundary_distances=self._boundary_distances, foreground_threshold=foreground_threshold,
+                                      center_distance_threshold=center_distance_threshold,
+                                      boundary_distance_threshold=boundary_distance_threshold)
         if prompts is None:
             return np.zeros(foreground.shape, dtype="uint32") if output_mode == "instance_segmentation" else []
 
@@ -955,11 +999,18 @@ class TiledAutomaticPromptGenerator(TiledInstanceSegmentationWithDecoder):
         if optimize_memory and (output_mode != "instance_segmentation" or refine_with_box_prompts):
             raise ValueError("Invalid settings")
         foreground = self._foreground
-        prompt_function = _derive_point_prompts if prompt_function is None else prompt_function
-        prompts = prompt_function(foreground, self._center_distances, self._boundary_distances,
-                                  foreground_threshold=foreground_threshold,
-                                  center_distance_threshold=center_distance_threshold,
-                                  boundary_distance_threshold=boundary_distance_threshold)
+        device_maps = getattr(self, "_device_maps", None)
+        if prompt_function is None and device_maps is not None:      # as in AutomaticPromptGenerator.generate, on the stitched maps
+            prompts = _derive_point_prompts_device(device_maps[0], device_maps[1], device_maps[2],
+                                                   foreground_threshold=foreground_threshold,
+                                                   center_distance_threshold=center_distance_threshold,
+                                                   boundary_distance_threshold=boundary_distance_threshold)
+        else:
+            prompt_function = _derive_point_prompts if prompt_function is None else prompt_function
+            prompts = prompt_function(foreground, self._center_distances, self._boundary_distances,
+                                      foreground_threshold=foreground_threshold,
+                                      center_distance_threshold=center_distance_threshold,
+                                      boundary_distance_threshold=boundary_distance_threshold)
         shape = foreground.shape
         if prompts is None:
             return np.zeros(shape, dtype="uint32") if output_mode == "instance_segmentation" else []

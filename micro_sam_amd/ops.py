@@ -1245,3 +1245,4 @@ from ._conv3d import column_sums, conv3d_k3, conv3d_k3_wgrad, instance_norm_appl
 from ._adapter import adapter_  # noqa: E402,F401  (csrc/adapter.hip; same arrangement)
 from ._tilemerge import paint_tiled, tiled_mask_overlaps  # noqa: E402,F401  (csrc/tilemerge.hip; same arrangement)
 from ._track import mask_moments, mask_shift  # noqa: E402,F401  (csrc/track.hip; same arrangement)
+from ._promptseeds import SeedCenters, seed_centers  # noqa: E402,F401  (csrc/labelprops.hip's msam_seed_centers; same arrangement)
