@@ -1198,6 +1198,40 @@ int msam_instance_norm_backward(const float* dy, int64_t ldy, const float* a, in
 int msam_column_sums_f32(const float* x, int64_t ldx, int64_t M, int32_t C, double* sums, void* workspace, int64_t workspace_bytes,
                          void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Merging per-slice instance segmentations across z (multi_dimensional_segmentation.merge_instance_segmentation_3d; reference
+ * micro_sam/multi_dimensional_segmentation.py:236-309 _preprocess_closing / _filter_z_extent, :312-382; csrc/merge3d.hip; DESIGN.md
+ * section 8.12): the passes over the label volume around the host's multicut.  labels: int32 [Z, H, W] contiguous, Z, H, W >= 1,
+ * H * W below 2^31, Z * H * W below 2^38.  Integer atomics whose result does not depend on their order (min / max / or): two calls
+ * agree bit for bit.  Kernels on `stream`, no allocation, no synchronisation, nothing read back.  A refusal returns non-zero with a
+ * message that names the entry point and leaves the outputs untouched.
+ * ------------------------------------------------------------------------------------------------- */
+/* out: int32 [Z, H, W] = _preprocess_closing(labels, gap), integer for integer.  gap >= 1; id_limit >= 1 is larger than every label.
+ * With fg = labels > 0, dil[z] = OR of fg[z'] over |z' - z| <= gap inside the volume and closed[z] = AND of dil[z'] over |z' - z| <= gap
+ * (binary closing with a z line, on the interior slices gap <= z < Z - gap), a running offset that starts at 1, slices in z order:
+ *   edge slice (z < gap or z >= Z - gap): the distinct non-zero ids become offset + rank, ascending; then offset += n for n > 0 ids,
+ *                  offset = 1 for an empty slice (the reference's own line);
+ *   interior     : the 8-connected components of closed[z] in the order of their first pixel in raster order; a component is KEPT when
+ *                  its pixels hold at most one distinct non-zero label of slice z; I = the labels found inside the others.  A pixel whose
+ *                  label is in I takes (kept components) + rank of its label in I, wherever it lies; every other pixel of a kept
+ *                  component takes the component's rank among the kept components that still own a pixel; every other pixel 0; all
+ *                  plus the offset.  offset += number of values present.
+ * result: DEVICE int32 [4] = the final offset (every value of out is below it); 0, or 1 (| 2) when a label is negative (>= id_limit):
+ * such a label reads as 0 and `out` is unspecified; the flag of the labelling (0 = complete, as msam_label_components_async); 0.
+ * out must not be labels.  workspace: the caller's, 4-byte aligned: 12 bytes per voxel of the interior slices + 8 bytes per (slice,
+ * 32 ids) + small per-slice tables (the query returns 0 for arguments the call refuses). */
+int64_t msam_close_gaps_workspace_bytes(int32_t Z, int32_t H, int32_t W, int32_t gap, int32_t id_limit);
+int msam_close_gaps(const int32_t* labels, int32_t Z, int32_t H, int32_t W, int32_t gap, int32_t id_limit, int32_t* out, int32_t* result,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+/* zr: int32 [n_ids, 2] = (the smallest, the largest slice in which the id occurs), (Z, -1) for an id that never occurs; id 0 is the
+ * background and is not tracked: its row is (Z, -1).  1 <= n_ids <= 2^30.  An id occurs in two slices when the two differ (the check
+ * of compute_edges_from_overlap); largest - smallest + 1 is the z extent of _filter_z_extent's bounding box.  flag: DEVICE int32 [1],
+ * 1 when a label lies outside [0, n_ids) (it is left out).  A memset and two launches. */
+int msam_label_z_ranges(const int32_t* labels, int32_t Z, int32_t H, int32_t W, int32_t n_ids, int32_t* zr, int32_t* flag, void* stream);
+/* out[p] = lut[labels[p]] for the n values of labels (1 <= n < 2^38), lut: int32 [n_lut]; where labels[p] lies outside [0, n_lut), 0 is
+ * written and flag (DEVICE int32 [1]) is set to 1.  out may be labels.  A memset and one launch. */
+int msam_apply_label_lut(const int32_t* labels, int64_t n, const int32_t* lut, int32_t n_lut, int32_t* out, int32_t* flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

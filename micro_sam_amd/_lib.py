@@ -299,6 +299,10 @@ _PROTOS = {
     "msam_paint_tiled": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "msam_mask_moments": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "msam_mask_shift": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "msam_close_gaps_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "msam_close_gaps": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "msam_label_z_ranges": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "msam_apply_label_lut": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _vp]),
 }
 OPTIONAL = set()
 

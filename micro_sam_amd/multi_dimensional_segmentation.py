@@ -559,19 +559,8 @@ def _filter_z_extent(segmentation: np.ndarray, min_z_extent: int) -> np.ndarray:
     return segmentation
 
 
-def merge_instance_segmentation_3d(slice_segmentation: np.ndarray, beta: float = 0.5, with_background: bool = True,
-                                   gap_closing: Optional[int] = None, min_z_extent: Optional[int] = None, verbose: bool = False,
-                                   device=None) -> np.ndarray:
-    """Reference :312-382: objects of consecutive slices are nodes joined by their normalised overlap; edge costs
-    ``compute_edge_costs(overlap)``, the multicut is solved on ``1 - costs`` (reference :365-373: a large overlap is attractive) and
-    every slice object takes its cluster's label.  ``with_background``: edges that touch label 0 are maximally repulsive (none is
-    emitted here: the background is not a node).  ``beta`` is accepted as in the reference, which hands it to the solver call only."""
-    if gap_closing is not None and gap_closing > 0:
-        slice_segmentation = _preprocess_closing(slice_segmentation, gap_closing)
-    uv_ids, overlaps = compute_edges_from_overlap(slice_segmentation, device=device)
-    if len(uv_ids) == 0:
-        return slice_segmentation
-    n_nodes = int(slice_segmentation.max()) + 1
+def _solve_node_labels(n_nodes: int, uv_ids: np.ndarray, overlaps: np.ndarray, with_background: bool) -> np.ndarray:
+    """Reference :365-376: costs from the overlaps, the multicut (GAEC + refinement, on the host), the background kept at label 0."""
     costs = compute_edge_costs(overlaps)
     if with_background:
         costs[(uv_ids == 0).any(axis=1)] = -8.0
@@ -579,6 +568,71 @@ def merge_instance_segmentation_3d(slice_segmentation: np.ndarray, beta: float =
     node_labels = multicut_refine(n_nodes, uv_ids, 1.0 - costs, node_labels)          # Kernighan-Lin style local search on GAEC's result
     if node_labels[0] != 0:                                 # keep the background at label 0
         node_labels = np.where(node_labels == node_labels[0], 0, np.where(node_labels < node_labels[0], node_labels + 1, node_labels))
+    return node_labels
+
+
+def _merge_instance_segmentation_3d_device(seg: torch.Tensor, with_background: bool, gap_closing: Optional[int],
+                                           min_z_extent: Optional[int]) -> torch.Tensor:
+    """``merge_instance_segmentation_3d`` with the label volume in device memory from end to end (csrc/merge3d.hip):
+    the gap closing, the uniqueness check and the z extents through per-id slice ranges, the overlap table, the lookup of the cluster
+    labels.  The edge list (a few thousand rows) goes to the host, the node labels come back; no voxel does.  Value for value the host
+    route's result."""
+    from . import ops
+    if seg.dtype != torch.int32 or seg.dim() != 3 or not seg.is_contiguous():
+        raise ValueError(f"merge_instance_segmentation_3d: a device volume must be a contiguous int32 [Z, H, W] tensor, got {seg.dtype} "
+                         f"{list(seg.shape)}")
+    if seg.numel() == 0:
+        return seg
+    lo, hi = (int(v) for v in torch.stack([seg.min(), seg.max()]).tolist())
+    if lo < 0:
+        raise ValueError("merge_instance_segmentation_3d: labels must not be negative")
+    if gap_closing is not None and gap_closing > 0:
+        seg, result = ops.close_gaps_z(seg, int(gap_closing), id_limit=hi + 1)
+        _, outside, incomplete, _ = result.tolist()
+        if incomplete or outside:
+            raise RuntimeError("micro_sam_amd: msam_close_gaps: the component labelling did not complete" if incomplete else
+                               "micro_sam_amd: msam_close_gaps: a label outside [0, id_limit)")
+        hi = int(seg.max())                              # (not final - 1: the offset falls back to 1 on an empty edge slice)
+    n_nodes = hi + 1
+    if seg.shape[0] >= 2:
+        zr, _ = ops.label_z_ranges(seg, n_nodes)
+        if bool(((zr[:, 1] >= 0) & (zr[:, 0] != zr[:, 1])).any()):
+            _check_ids_unique_per_slice(seg.cpu().numpy())       # raises the host's message (the error path may copy the volume)
+            raise ValueError("compute_edges_from_overlap: object ids must be unique across slices")
+    uv_ids, overlaps = edges_from_overlap_table(ops.slice_overlaps(seg))
+    if len(uv_ids) == 0:
+        return seg
+    node_labels = _solve_node_labels(n_nodes, uv_ids, overlaps, with_background)
+    lut = torch.as_tensor(node_labels.astype(np.int32), device=seg.device)
+    out, _ = ops.apply_label_lut(seg, lut)
+    if min_z_extent is not None and min_z_extent > 0:
+        n_out = int(node_labels.max()) + 1
+        zr, _ = ops.label_z_ranges(out, n_out)
+        keep = (zr[:, 1] < 0) | (zr[:, 1] - zr[:, 0] + 1 >= int(min_z_extent))
+        ids = torch.arange(n_out, dtype=torch.int32, device=seg.device)
+        ops.apply_label_lut(out, torch.where(keep, ids, torch.zeros_like(ids)), out=out)
+    return out
+
+
+def merge_instance_segmentation_3d(slice_segmentation, beta: float = 0.5, with_background: bool = True,
+                                   gap_closing: Optional[int] = None, min_z_extent: Optional[int] = None, verbose: bool = False,
+                                   device=None):
+    """Reference :312-382: objects of consecutive slices are nodes joined by their normalised overlap; edge costs
+    ``compute_edge_costs(overlap)``, the multicut is solved on ``1 - costs`` (reference :365-373: a large overlap is attractive) and
+    every slice object takes its cluster's label.  ``with_background``: edges that touch label 0 are maximally repulsive (none is
+    emitted here: the background is not a node).  ``beta`` is accepted as in the reference, which hands it to the solver call only.
+
+    A numpy volume takes the host code below (only the overlap count runs on the device).  A device int32 [Z, H, W] tensor stays on
+    the device (``_merge_instance_segmentation_3d_device``) and a device tensor with the same values comes back."""
+    if torch.is_tensor(slice_segmentation):
+        return _merge_instance_segmentation_3d_device(slice_segmentation, with_background, gap_closing, min_z_extent)
+    if gap_closing is not None and gap_closing > 0:
+        slice_segmentation = _preprocess_closing(slice_segmentation, gap_closing)
+    uv_ids, overlaps = compute_edges_from_overlap(slice_segmentation, device=device)
+    if len(uv_ids) == 0:
+        return slice_segmentation
+    n_nodes = int(slice_segmentation.max()) + 1
+    node_labels = _solve_node_labels(n_nodes, uv_ids, overlaps, with_background)
     segmentation = node_labels[slice_segmentation].astype(slice_segmentation.dtype)
     if min_z_extent is not None and min_z_extent > 0:
         segmentation = _filter_z_extent(segmentation, min_z_extent)
@@ -588,12 +642,36 @@ def merge_instance_segmentation_3d(slice_segmentation: np.ndarray, beta: float =
 def automatic_3d_segmentation(volume: np.ndarray, predictor, segmentor, embedding_path=None, with_background: bool = True,
                               gap_closing: Optional[int] = None, min_z_extent: Optional[int] = None,
                               tile_shape: Optional[Tuple[int, int]] = None, halo: Optional[Tuple[int, int]] = None,
-                              verbose: bool = False, return_embeddings: bool = False, batch_size: int = 1, **kwargs):
-    """Reference :419-481: per-slice segmentation (``segment_slices``) merged across z (``merge_instance_segmentation_3d``)."""
-    segmentation, image_embeddings = segment_slices(volume, predictor, segmentor, embedding_path=embedding_path, verbose=verbose,
-                                                    tile_shape=tile_shape, halo=halo, batch_size=batch_size, **kwargs)
-    segmentation = merge_instance_segmentation_3d(segmentation, beta=0.5, with_background=with_background, gap_closing=gap_closing,
-                                                  min_z_extent=min_z_extent, verbose=verbose, device=predictor.device)
+                              verbose: bool = False, return_embeddings: bool = False, batch_size: int = 1,
+                              device_merge: Optional[bool] = None, **kwargs):
+    """Reference :419-481: per-slice segmentation (``segment_slices``) merged across z (``merge_instance_segmentation_3d``).
+
+    ``device_merge`` (not in the reference; None = on a GPU): the merge keeps the label volume in device memory.  Where the slice
+    loop runs as the device pipeline its labels never leave HBM before the merge and the result is downloaded once; otherwise what
+    ``segment_slices`` returned is uploaded (as the overlap count does anyway).  The same uint32 volume, value for value, either way."""
+    if device_merge is None:
+        device_merge = str(predictor.device).startswith("cuda") and torch.cuda.is_available()
+    merge_kw = dict(beta=0.5, with_background=with_background, gap_closing=gap_closing, min_z_extent=min_z_extent, verbose=verbose)
+    if not device_merge:
+        segmentation, image_embeddings = segment_slices(volume, predictor, segmentor, embedding_path=embedding_path, verbose=verbose,
+                                                        tile_shape=tile_shape, halo=halo, batch_size=batch_size, **kwargs)
+        segmentation = merge_instance_segmentation_3d(segmentation, device=predictor.device, **merge_kw)
+        return (segmentation, image_embeddings) if return_embeddings else segmentation
+    dev = _lib.require_gpu(predictor.device)
+    res = None
+    lanes = kwargs.get("decode_lanes", 3)
+    generate_kw = {k: v for k, v in kwargs.items() if k != "decode_lanes"}
+    assert volume.ndim == 3
+    if lanes > 0 and _can_pipeline(volume, predictor, segmentor, embedding_path, tile_shape, generate_kw):
+        res = _segment_slices_pipelined(volume, predictor, segmentor, batch_size, lanes, True, generate_kw)
+    if res is not None:
+        labels, image_embeddings = res
+    else:
+        segmentation, image_embeddings = segment_slices(volume, predictor, segmentor, embedding_path=embedding_path, verbose=verbose,
+                                                        tile_shape=tile_shape, halo=halo, batch_size=batch_size, **kwargs)
+        labels = torch.as_tensor(np.ascontiguousarray(segmentation).astype(np.int32, copy=False)).to(dev)
+    merged = merge_instance_segmentation_3d(labels, **merge_kw)
+    segmentation = util.fetch_to_host(merged, tag="merge3d").view(np.uint32) if merged.numel() else np.zeros(tuple(merged.shape), np.uint32)
     return (segmentation, image_embeddings) if return_embeddings else segmentation
 
 

@@ -1246,3 +1246,4 @@ from ._adapter import adapter_  # noqa: E402,F401  (csrc/adapter.hip; same arran
 from ._tilemerge import paint_tiled, tiled_mask_overlaps  # noqa: E402,F401  (csrc/tilemerge.hip; same arrangement)
 from ._track import mask_moments, mask_shift  # noqa: E402,F401  (csrc/track.hip; same arrangement)
 from ._promptseeds import SeedCenters, seed_centers  # noqa: E402,F401  (csrc/labelprops.hip's msam_seed_centers; same arrangement)
+from ._merge3d import apply_label_lut, close_gaps_z, label_z_ranges  # noqa: E402,F401  (csrc/merge3d.hip; same arrangement)
