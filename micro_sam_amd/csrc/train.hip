@@ -246,7 +246,11 @@ __global__ __launch_bounds__(256) void attn_fwd_rowblock_kernel(const float* __r
         m = mn;
     }
     const float M = block_max256(m, red);
-    const float r = __expf(m - M);                       // threads without a key: m = -3e38 -> r = 0
+    // A thread without a key would keep m = -3e38 and get r = 0.  The launcher takes this route only for Nk >= 1024, so every one of
+    // the 256 threads has at least four keys and that case does not occur today; the line stays correct for it on purpose (a
+    // route condition lowered below 256 keys needs no change here; tests/test_train_kernels_host_emulation.py runs the kernel with
+    // 200 keys on the CPU).
+    const float r = __expf(m - M);
     const float L = block_sum256(l * r, red);
     float* op = out + ((long)bh * Nq + i) * D;
 #pragma unroll

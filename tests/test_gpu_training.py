@@ -5,7 +5,10 @@ loss curve of 20 SamTrainer steps against the same training run on the fp32 orac
 Tolerances: fp32 kernels (LayerNorm, attention) 1e-4 relative; bf16-operand GEMMs (AMP-like) 2e-2 relative on outputs and
 gradients; per-parameter gradient cosine similarity >= 0.99; SGD loss curve within 1 % over the first five steps, 5 % at
 every step and 2 % on average (measured with lr 2e-3: 0.0 / 0.0 / 0.1 / 1.6 / 3.5 % over the first five steps, then the
-noisy trajectories separate - bf16 gradient noise is amplified by the training dynamics, not by the kernels)."""
+noisy trajectories separate - bf16 gradient noise is amplified by the training dynamics, not by the kernels).
+
+The attention kernels' edge and range cases (route edges, exact gathers, float64 rounding bounds, lse / delta) are in
+tests/test_gpu_train_attention.py."""
 import copy
 import os
 import random

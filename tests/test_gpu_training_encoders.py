@@ -3,7 +3,10 @@ the rel-pos attention kernels and the wide LayerNorm backward against torch auto
 prompt encoder (values + parameter gradients) against the fp32 oracle's autograd, and a few optimiser steps of the whole model.
 
 Tolerances as in tests/test_gpu_training.py: fp32 kernels 1e-4 relative (2e-4 for attention gradients); bf16-operand GEMM
-compositions: outputs 2 % of the output range, per-parameter gradient cosine similarity >= 0.99."""
+compositions: outputs 2 % of the output range, per-parameter gradient cosine similarity >= 0.99.
+
+The attention kernels' edge and range cases (route edges, exact gathers, float64 rounding bounds, lse / delta) are in
+tests/test_gpu_train_attention.py."""
 import os
 
 import numpy as np
