@@ -621,6 +621,28 @@ int msam_decoder_forward_embeddings(const msam_decoder_t* dec, const void* const
                                     int32_t P, int32_t multimask, float* low_res, float* iou, void* workspace,
                                     int64_t workspace_bytes, void* stream);
 
+/* The decoder's small kernels one at a time (csrc/decoder.hip), as a decode launches them: for the tests that hold each kernel to a
+ * float64 reference (tests/decoder_kernels_ref.py).  A decode does not go through these.  16-bit = msam_decoder_dtype().  Bad arguments
+ * (null pointers, P <= 0, Nt / Ns out of range, a group that does not fit Nt or kv_shared) return 1 before any launch.
+ * msam_dec_token_self_attention: q, k, v, out 16-bit [P Nt, 256] (8 heads x 32), 1 <= Nt <= 16.
+ * msam_dec_t2i_attention: q_tok, out 16-bit [P Nt, 128] (8 heads x 16); k_img 16-bit head-major [Pk, 8, 4096, 16], vT 16-bit
+ *   [Pk, 128, 4096], Pk = 1 with kv_shared, P otherwise.  group 0: one workgroup per (prompt, head), 1 <= Nt <= 16; group 4 / 8 / 16:
+ *   the shared-K/V kernel with that many prompts per workgroup (kv_shared = 1, Nt <= 8).
+ * msam_dec_source_stream: src_f32 fp32 / src16 16-bit [4096, 256] = embedding^T + no_mask_embed; then keys16 16-bit [P, 4096, 256] =
+ *   the per-prompt source from mask_input (fp32 [P, 1, 256, 256], reads src_f32) or from dense (fp32 [P, 256, 64, 64]); neither: keys16
+ *   is not written and may be NULL.
+ * msam_dec_tokens_from_sparse: tokens / queries fp32, queries16 16-bit [P (5 + Ns), 256] = [5 output tokens; sparse[p]], 0 <= Ns <= 11.
+ * msam_dec_add_cast: out_a = round16(a + b) (b NULL: round16(a)); with out_b also out_b = round16(a) (needs b); n % 4 == 0. */
+int msam_dec_token_self_attention(const void* q, const void* k, const void* v, int32_t P, int32_t Nt, void* out, void* stream);
+int msam_dec_t2i_attention(const void* q_tok, const void* k_img, const void* vT, int32_t kv_shared, int32_t group, int32_t P,
+                           int32_t Nt, void* out, void* stream);
+int msam_dec_source_stream(const msam_decoder_t* dec, const msam_mask_prompt_t* mask_w, const float* embedding,
+                           const float* mask_input, const float* dense, int32_t P, float* src_f32, void* src16, void* keys16,
+                           void* stream);
+int msam_dec_tokens_from_sparse(const msam_decoder_t* dec, const float* sparse, int32_t Ns, int32_t P, float* tokens,
+                                float* queries, void* queries16, void* stream);
+int msam_dec_add_cast(const float* a, const float* b, void* out_a, void* out_b, int64_t n, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * Mask post-processing:  Sam.postprocess_masks + AMGBase._to_mask_data
  * (micro_sam/instance_segmentation.py:229-255, micro_sam/_vendored.py:33-152)

@@ -220,6 +220,11 @@ _PROTOS = {
     "msam_decoder_prepare_image": (_i32, [C.POINTER(DecoderParams), _vp, _vp, _vp, _vp, _i64, _vp]),
     "msam_decoder_workspace_bytes": (_i64, [_i32]),
     "msam_prompt_encode": (_i32, [C.POINTER(DecoderParams), C.POINTER(MaskPromptParams), _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "msam_dec_token_self_attention": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "msam_dec_t2i_attention": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "msam_dec_source_stream": (_i32, [C.POINTER(DecoderParams), C.POINTER(MaskPromptParams), _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "msam_dec_tokens_from_sparse": (_i32, [C.POINTER(DecoderParams), _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "msam_dec_add_cast": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "msam_decoder_forward_embeddings": (_i32, [C.POINTER(DecoderParams), _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp,
                                                _i64, _vp]),
     "msam_decoder_forward": (_i32, [C.POINTER(DecoderParams), _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp,

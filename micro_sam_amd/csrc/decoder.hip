@@ -820,6 +820,89 @@ extern "C" int msam_prompt_encode(const msam_decoder_t* dec, const msam_mask_pro
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------ kernel-level entry points
+// The decoder's small kernels one at a time, for the tests that hold each of them to a float64 reference (tests/decoder_kernels_ref.py).
+// Validated launch wrappers around the kernels as a decode launches them; decoder_run does not go through these.
+
+extern "C" int msam_dec_token_self_attention(const void* q, const void* k, const void* v, int32_t P, int32_t Nt, void* out, void* stream) {
+    if (!q || !k || !v || !out) { msam_set_error("msam_dec_token_self_attention: null argument"); return 1; }
+    if (P <= 0) { msam_set_error("msam_dec_token_self_attention: P must be positive"); return 1; }
+    if (Nt < 1 || Nt > 16) { msam_set_error("msam_dec_token_self_attention: 1 .. 16 tokens per prompt"); return 1; }
+    hipLaunchKernelGGL(token_self_attn_kernel, dim3(P), dim3(128), 0, (hipStream_t)stream, (const u16*)q, (const u16*)k, (const u16*)v,
+                       Nt, (u16*)out);
+    return msam_check_launch("token_self_attn");
+}
+
+extern "C" int msam_dec_t2i_attention(const void* q_tok, const void* k_img, const void* vT, int32_t kv_shared, int32_t group, int32_t P,
+                                      int32_t Nt, void* out, void* stream) {
+    if (!q_tok || !k_img || !vT || !out) { msam_set_error("msam_dec_t2i_attention: null argument"); return 1; }
+    if (P <= 0) { msam_set_error("msam_dec_t2i_attention: P must be positive"); return 1; }
+    if (Nt < 1 || Nt > 16) { msam_set_error("msam_dec_t2i_attention: 1 .. 16 tokens per prompt"); return 1; }
+    if (group != 0 && group != 4 && group != 8 && group != 16) { msam_set_error("msam_dec_t2i_attention: group is 0, 4, 8 or 16"); return 1; }
+    if (group != 0 && (!kv_shared || Nt > 8)) {
+        msam_set_error("msam_dec_t2i_attention: a prompt group needs the shared K / V^T and at most 8 tokens per prompt");
+        return 1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const u16 *qp = (const u16*)q_tok, *kp = (const u16*)k_img, *vp = (const u16*)vT;
+    if (group == 0) {
+        hipLaunchKernelGGL(t2i_attn_kernel, dim3(P * 8), dim3(256), 0, s, qp, kp, vp, kv_shared ? 1 : 0, Nt, (u16*)out);
+    } else {
+        const dim3 grid(((P + group - 1) / group) * 8);
+        if (group == 4) hipLaunchKernelGGL(t2i_shared_kernel<4>, grid, dim3(256), 0, s, qp, kp, vp, P, Nt, (u16*)out);
+        else if (group == 8) hipLaunchKernelGGL(t2i_shared_kernel<8>, grid, dim3(256), 0, s, qp, kp, vp, P, Nt, (u16*)out);
+        else hipLaunchKernelGGL(t2i_shared_kernel<16>, grid, dim3(256), 0, s, qp, kp, vp, P, Nt, (u16*)out);
+    }
+    return msam_check_launch("t2i_attn");
+}
+
+extern "C" int msam_dec_source_stream(const msam_decoder_t* dec, const msam_mask_prompt_t* mask_w, const float* embedding,
+                                      const float* mask_input, const float* dense, int32_t P, float* src_f32, void* src16, void* keys16,
+                                      void* stream) {
+    if (!dec || !embedding || !src_f32 || !src16) { msam_set_error("msam_dec_source_stream: null argument"); return 1; }
+    if (P <= 0) { msam_set_error("msam_dec_source_stream: P must be positive"); return 1; }
+    if (mask_input && dense) { msam_set_error("msam_dec_source_stream: a mask prompt or a dense embedding, not both"); return 1; }
+    if (mask_input && !mask_w) { msam_set_error("msam_dec_source_stream: mask prompts need the mask_downscaling weights"); return 1; }
+    if ((mask_input || dense) && !keys16) { msam_set_error("msam_dec_source_stream: null keys output"); return 1; }
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(src_prepare_kernel, dim3(T / 32, C / 32), dim3(256), 0, s, embedding, dec->no_mask, src_f32, (u16*)src16);
+    if (int e = msam_check_launch("src_prepare")) return e;
+    if (mask_input) {
+        hipLaunchKernelGGL(mask_src_kernel, dim3(64, P), dim3(256), 0, s, mask_input, *mask_w, (const float*)src_f32, dec->no_mask,
+                           (u16*)keys16, (float*)nullptr);
+        return msam_check_launch("mask_src");
+    }
+    if (dense) {
+        hipLaunchKernelGGL(dense_src_kernel, dim3(T / 32, C / 32, P), dim3(256), 0, s, embedding, dense, (u16*)keys16);
+        return msam_check_launch("dense_src");
+    }
+    return 0;
+}
+
+extern "C" int msam_dec_tokens_from_sparse(const msam_decoder_t* dec, const float* sparse, int32_t Ns, int32_t P, float* tokens,
+                                           float* queries, void* queries16, void* stream) {
+    if (!dec || !tokens || !queries || !queries16) { msam_set_error("msam_dec_tokens_from_sparse: null argument"); return 1; }
+    if (P <= 0) { msam_set_error("msam_dec_tokens_from_sparse: P must be positive"); return 1; }
+    if (Ns < 0 || Ns > 11) { msam_set_error("msam_dec_tokens_from_sparse: 0 .. 11 sparse tokens per prompt"); return 1; }
+    if (Ns > 0 && !sparse) { msam_set_error("msam_dec_tokens_from_sparse: Ns > 0 needs the sparse embeddings"); return 1; }
+    hipLaunchKernelGGL(tokens_from_sparse_kernel, dim3(P), dim3(256), 0, (hipStream_t)stream, dec->out_tokens, sparse, Ns, P, 5 + Ns,
+                       tokens, queries, (u16*)queries16);
+    return msam_check_launch("tokens_from_sparse");
+}
+
+extern "C" int msam_dec_add_cast(const float* a, const float* b, void* out_a, void* out_b, int64_t n, void* stream) {
+    if (!a || !out_a) { msam_set_error("msam_dec_add_cast: null argument"); return 1; }
+    if (out_b && !b) { msam_set_error("msam_dec_add_cast: the two-output form needs b"); return 1; }
+    if (n <= 0 || n % 4 != 0) { msam_set_error("msam_dec_add_cast: n must be a positive multiple of 4"); return 1; }
+    const long n4 = n / 4;
+    if (out_b) {
+        hipLaunchKernelGGL(add_cast2_kernel, dim3(grid_for(n4)), dim3(256), 0, (hipStream_t)stream, a, b, (u16*)out_a, (u16*)out_b, n4);
+        return msam_check_launch("add_cast2");
+    }
+    hipLaunchKernelGGL(add_cast_kernel, dim3(grid_for(n4)), dim3(256), 0, (hipStream_t)stream, a, b, (u16*)out_a, n4);
+    return msam_check_launch("add_cast");
+}
+
 namespace {
 int decoder_run(const msam_decoder_t* dec, const msam_mask_prompt_t* mask_w, const void* consts,
                 const void* image_state, const float* points, const int32_t* labels, int32_t Np,

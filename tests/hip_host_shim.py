@@ -393,8 +393,8 @@ static inline void __builtin_amdgcn_s_barrier() { block_sync(); }
 #define __restrict__
 #define __shared__ static
 // one workgroup of 256 threads after the other: f() is the kernel call
-template <class F> static void launch_grid(int gx, int gy, F f, int threads = 256) {
-    gridDim = {gx, gy, 1};
+template <class F> static void launch_grid(int gx, int gy, F f, int threads = 256, int gz = 1) {
+    gridDim = {gx, gy, gz};
     const int nw = (threads + 63) / 64;
     constexpr size_t STACK = 256 * 1024;
     BlockBarrier bar, next;
@@ -409,9 +409,10 @@ template <class F> static void launch_grid(int gx, int gy, F f, int threads = 25
             wv->entry = [](void* a) { (*(F*)a)(); };
             WV = wv;
             const int lanes = std::min(64, threads - w * 64);
+            for (int bz = 0; bz < gz; ++bz)
             for (int by = 0; by < gy; ++by)
                 for (int bx = 0; bx < gx; ++bx) {
-                    blockIdx = {bx, by, 0};
+                    blockIdx = {bx, by, bz};
                     if (w == 0) { std::lock_guard<std::mutex> lk(bar.m); bar.expected = nw; bar.arrived = 0; }
                     next.arrive_and_wait();                                    // the block barrier is set up; LDS of the last block is free
                     for (int l = 0; l < 64; ++l) {
@@ -507,7 +508,7 @@ static inline hipError_t hipMemcpyFromSymbol(void* d, const void* sym, size_t n)
 #define hipLaunchKernelGGL(kern_, grid_, block_, shmem_, stream_, ...)                                 \
     do {                                                                                               \
         const dim3 g__ = (grid_), b__ = (block_);                                                      \
-        launch_grid((int)g__.x, (int)g__.y, [=] { kern_(__VA_ARGS__); }, (int)b__.x);                  \
+        launch_grid((int)g__.x, (int)g__.y, [=] { kern_(__VA_ARGS__); }, (int)b__.x, (int)g__.z);      \
     } while (0)
 """
 

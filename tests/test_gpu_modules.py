@@ -48,8 +48,12 @@ def test_prompt_encoder_forward(ctx, kind):
         assert sparse.shape == (6, 0, 256)
     else:
         assert sparse.shape == rs.shape
-        assert (sparse.cpu() - rs).abs().max().item() < 2e-4            # sinf / cosf of arguments up to ~ 2 pi * 4
+        # module-level comparison with the fp32 oracle on interior points with labels 0 / 1: a coarse net (a hundred times the rounding
+        # error of a correct kernel).  The kernels themselves - every label, coordinates outside the frame, degenerate boxes, both GELU
+        # forms of the mask embedding - are held to float64 rounding bounds in tests/test_gpu_decoder_kernels.py
+        assert (sparse.cpu() - rs).abs().max().item() < 2e-4
     assert dense.shape == (6, 256, 64, 64)
+    # (2e-3 is wider than the 1e-4 .. 5e-4 between the two GELU forms: it does not tell them apart; tests/decoder_kernels_ref.py does)
     assert (dense.cpu() - rd).abs().max().item() < (2e-3 if mk is not None else 1e-6)
     pe = sam.prompt_encoder.get_dense_pe()
     assert (pe.cpu() - S.get_dense_pe(ctx["sd"])).abs().max().item() < 2e-4
