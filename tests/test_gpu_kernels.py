@@ -4,7 +4,8 @@ bf16 rounding (rel 1e-2).  These are coarse nets; the kernel families are pinned
 tests/test_gpu_gemm_routes.py, the encoder attention in tests/test_gpu_attention.py, the folded decoder attention in
 tests/test_gpu_decoder_fold.py, the fused up-scaling in tests/test_gpu_upscale_fused.py, fine-tuning's attention in
 tests/test_gpu_train_attention.py, and the small kernels of csrc/decoder.hip (prompt encoding, token self attention, token->image
-attention, the source stream) in tests/test_gpu_decoder_kernels.py with tests/decoder_kernels_ref.py."""
+attention, the source stream) in tests/test_gpu_decoder_kernels.py with tests/decoder_kernels_ref.py.  The kernels of the split16
+precision mode (csrc/strict.hip) are pinned in tests/test_gpu_split16_kernels.py with tests/split16_ref.py."""
 import math
 
 import pytest

@@ -2,7 +2,9 @@
 the reference CPU path (the fp32 oracle): the embedding, the low-res logits, and - the north-star statement itself - the per-instance mask
 IoU, the keep set and the instance ids of AutomaticMaskGenerator on the benchmarked configuration, against the seven committed fp32
 goldens (tests/golden/*.npz).  The default 16-bit path reaches 96 - 100 % of the instances at IoU >= 0.999 on these cases
-(tests/test_gpu_parity_iou.py); the strict mode is the point of the speed / parity curve that meets the contract.  Reports go to
+(tests/test_gpu_parity_iou.py); the strict mode is the point of the speed / parity curve that meets the contract.  The split16
+mode's kernels are pinned one by one, against fp64 references and elementwise rounding bounds, in tests/test_gpu_split16_kernels.py
+(tests/split16_ref.py); this file covers the mode end to end.  Reports go to
 gpurun_out/parity_strict.json (-> profiles/)."""
 import json
 import os
