@@ -99,7 +99,11 @@ int msam_gemm_group_bf16(const msam_gemm_t* items, int32_t n, void* stream);
  * out = epi(A[M,K] * W[N,K]^T), A / W / out bf16, contiguous rows (lda = K, ldw = K).  Same epilogue vocabulary as
  * msam_gemm_bf16 (bias, row-indexed table on the first table_cols columns, bf16 residual, ln_mode 1/2 for N == 256),
  * or kv_split: N == 256: k_out <- columns 0..127 as [M,128], vT_out <- columns 128..255 as [M/tokens,128,tokens];
- * N == 128: all columns to vT_out transposed (k_out unused).  ln_mode 2 is also available for N == 128. */
+ * N == 128: all columns to vT_out transposed (k_out unused).  ln_mode 2 is also available for N == 128.
+ * The table is added four columns at a time: table_cols must be a non-negative multiple of 4, anything else is
+ * refused; table_ld must keep every table row 16-byte aligned (a multiple of 4 as well - not checked).  kv_split needs
+ * tokens > 0 with tokens % 64 == 0 and M % tokens == 0; M is a positive multiple of 64.  Status 1 = refused: nothing was
+ * launched and no output was written. */
 typedef struct {
     const void* A; const void* W; int32_t M, N, K;
     const float* bias;

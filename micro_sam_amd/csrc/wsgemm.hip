@@ -243,7 +243,13 @@ int launch(const u16* A, const u16* W, int M, const WsEpi& e, hipStream_t s) {
 extern "C" int msam_wsgemm_bf16(const msam_wsgemm_t* p, void* stream) {
     if (!p || !p->A || !p->W) { msam_set_error("msam_wsgemm_bf16: null operand"); return 1; }
     if (p->M <= 0 || p->M % 64) { msam_set_error("msam_wsgemm_bf16: M must be a positive multiple of 64"); return 1; }
-    if (p->kv_split && (!p->vT_out || (p->N == 256 && !p->k_out) || p->tokens % 64 || p->M % p->tokens || p->ln_mode)) {
+    // the epilogue adds the table four columns at a time (one float4 per lane): a width that is no multiple of 4 would add
+    // the table to the columns up to the next multiple and read past the end of each table row
+    if (p->table && (p->table_cols < 0 || p->table_cols % 4)) {
+        msam_set_error("msam_wsgemm_bf16: table_cols must be a non-negative multiple of 4");
+        return 1;
+    }
+    if (p->kv_split && (!p->vT_out || (p->N == 256 && !p->k_out) || p->tokens <= 0 || p->tokens % 64 || p->M % p->tokens || p->ln_mode)) {
         msam_set_error("msam_wsgemm_bf16: bad kv-split / transposed-output arguments");
         return 1;
     }

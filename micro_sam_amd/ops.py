@@ -592,6 +592,7 @@ def wsgemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
         _t("table", table, _F32, (None, None), dev)
         _need(0 <= table_cols <= min(N, table.shape[1]) and table.shape[0] > 0,
               f"table_cols = {table_cols} must lie in [0, min(N, table.shape[1])] with table {list(table.shape)}, N = {N}")
+        _need(table_cols % 4 == 0, f"table_cols = {table_cols} must be a multiple of 4 (the kernel adds the table four columns at a time)")
         p.table, p.table_rows, p.table_cols, p.table_ld = table.data_ptr(), table.shape[0], table_cols, table.shape[1]
     if resid is not None:
         _t("resid", resid, d16, (None, N), dev)

@@ -324,6 +324,7 @@ TABLE = [
           skip={"bits:strides": CONVERTED, **{f"{n}:{k}": CONVERTED for n in ("boxes_xyxy", "areas", "scores") for k in ("dtype", "strides", "device")}}),
     Entry("ops", "wsgemm", _wsgemm_kw, ["msam_wsgemm_bf16"], free={"a:0", "w:0", "table:0", "table:1"}, blame={"a:size1": "w"},
           scalars=[("resid_rows > resid.shape[0]", {"resid_rows": 8}, "resid"), ("table_cols > table.shape[1]", {"table_cols": 192}, "table"),
+                   ("table_cols no multiple of 4", {"table_cols": 6}, "table_cols"),
                    ("kv_split_tokens does not divide M", {"kv_split_tokens": 3, "out": None, "ln_mode": 0}, "kv_split_tokens")]),
     Entry("ops", "amg_generate_labels", lambda: dict(iou=z(3), stability=z(3), boxes=z(3, 4, dt=i32), area=z(3, dt=i32), bits=z(3, 2, 50, dt=i32),
                                                      shape=(40, 50), crop_box=(0, 0, 50, 40), pred_iou_thresh=0.5, stability_score_thresh=0.5, box_nms_thresh=0.5),

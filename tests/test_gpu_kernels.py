@@ -1,7 +1,7 @@
 """Kernel-level parity (through the C ABI) against plain torch fp32 on the same bf16-rounded operands.
 Tolerances: fp32 outputs differ from torch only by accumulation order (abs 1e-3 on O(10) values); bf16 outputs by one
 bf16 rounding (rel 1e-2).  These are coarse nets; the kernel families are pinned to float64 references, file by file: the GEMM family in
-tests/test_gpu_gemm_routes.py, the encoder attention in tests/test_gpu_attention.py, the folded decoder attention in
+tests/test_gpu_gemm_routes.py, the weights-stationary decoder GEMM in tests/test_gpu_wsgemm.py, the encoder attention in tests/test_gpu_attention.py, the folded decoder attention in
 tests/test_gpu_decoder_fold.py, the fused up-scaling in tests/test_gpu_upscale_fused.py, fine-tuning's attention in
 tests/test_gpu_train_attention.py, and the small kernels of csrc/decoder.hip (prompt encoding, token self attention, token->image
 attention, the source stream) in tests/test_gpu_decoder_kernels.py with tests/decoder_kernels_ref.py.  The kernels of the split16
